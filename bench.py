@@ -5,18 +5,31 @@ high-dimensional Rosenbrock settings, hmc.rs:763-780).
 A "step" is one HMC transition of every chain (L leapfrogs each). The timed
 region runs --steps transitions with every state collected on the device,
 bracketed by a barrier and a device synchronize on both sides; the time is
-the maximum over ranks. The split-R-hat / ESS of those draws follows (RCCL
+the maximum over ranks. A plain run does only that: set-up, the warm-up, the
+timed transitions, --dump-outputs if given, and the result line.
+
+With --full the split-R-hat / ESS of those draws follows (RCCL
 all-gather of per-split-chain summaries when N > 1), and a separately timed
 ESS leg runs cfg2's own schedule (n_discard 100, n_collect 100; hmc.rs:763-780)
-from the same start, so that ESS/s does not depend on --steps/--warmup.
+from the same start, so that ESS/s does not depend on --steps/--warmup; then
+the other BASELINE configs, the HBM ceilings, the host-output path, the
+north-star shape and the CPU baselines.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
+--dump-outputs DIR writes what the timed call returned, after the clock has
+stopped: DIR/positions.npy, the collected draws [rows, chains, dim] of the
+last timed transitions (every row while they fit in DUMP_BUDGET_BYTES, else a
+seeded sample of the rows that keeps the last; the row numbers are in the
+line's "outputs"), and DIR/accept_counts.npy, the accepted transitions of
+each chain in it. The start positions and every random stream are seeded, so the
+same arguments give the same files from run to run and from build to build.
+
 Prints one JSON line (rank 0). Every field of the N = 1 line is also in the
-N > 1 line: the rank-0-only measurements (copy ceiling, per-leapfrog HBM
-kernel, host-output path, CPU baseline) run on rank 0 after the timed region
-while the other ranks wait at the closing barrier.
+N > 1 line: the rank-0-only measurements of --full (copy ceiling, per-leapfrog
+HBM kernel, host-output path, CPU baseline) run on rank 0 after the timed
+region while the other ranks wait at the closing barrier.
 """
 from __future__ import annotations
 
@@ -51,6 +64,13 @@ def parse(argv=None):
     p.add_argument("--eps", type=float, default=0.01)
     p.add_argument("--dtype", default="f32", choices=["f32", "f64"])
     p.add_argument("--layout", default="", help="lanes,elems override")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed transitions, write the draws they collected and the accept counts "
+                        "to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run everything else the benchmark measures (the options "
+                        "below): diagnostics of the timed draws, ESS legs, the other BASELINE configs, HBM "
+                        "ceilings, host-output path, north-star shape, CPU baselines")
     p.add_argument("--ess-discard", type=int, default=100, help="ESS leg burn-in (cfg2: 100)")
     p.add_argument("--ess-collect", type=int, default=100, help="ESS leg draws (cfg2: 100)")
     p.add_argument("--ess-long-discard", type=int, default=4000,
@@ -247,6 +267,18 @@ class GpuBench:
 
     def diagnostics(self, ds, comm):
         return comm.split_rhat_ess(ds) if comm is not None else ds.split_rhat_ess()
+
+    def outputs(self, sampler, ds):
+        """What the timed call handed its caller, on the host: the collected
+        draws (the rows and chains of dump_sample, each row one strided
+        device-to-host copy) and the same chains' accept counts."""
+        rows, n_chains = dump_sample(ds.n_collect, ds.n_chains, ds.dim, np.dtype(ds.dtype).itemsize)
+        if len(rows) == ds.n_collect:
+            pos = ds.block(0, ds.n_collect, 0, n_chains)
+        else:
+            pos = np.concatenate([ds.block(r, 1, 0, n_chains) for r in rows])
+        acc = np.asarray(sampler.accept_counts()[:n_chains], dtype=np.float64)
+        return {"positions": pos, "accept_counts": acc}, rows
 
     def copy_ceiling(self, nbytes=1 << 30, reps=5):
         """Empirical HBM ceiling on this box: a 1 GiB
@@ -589,6 +621,39 @@ def load_pmc(C, D, L, dtype, steps):
     return traffic, issue
 
 
+# of --dump-outputs' positions.npy; the accept counts add 8 bytes per kept
+# chain, at most 3 MiB x 8 / (dim x itemsize) <= 6 MiB: under 64 MB in all
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_sample(n_rows, n_chains, dim, itemsize):
+    """The rows (collected transitions) and the leading chains of the timed
+    draws that --dump-outputs keeps: everything while it fits in
+    DUMP_BUDGET_BYTES, else the leading chains that fit in a sixteenth of it
+    and a seeded sample of the rows, the last one always among them."""
+    keep_chains = max(1, min(n_chains, DUMP_BUDGET_BYTES // 16 // (dim * itemsize)))
+    k = max(1, min(n_rows, DUMP_BUDGET_BYTES // (keep_chains * dim * itemsize)))
+    if k == n_rows:
+        return list(range(n_rows)), keep_chains
+    pick = np.random.default_rng(42).choice(n_rows - 1, size=k - 1, replace=False)
+    return sorted(int(r) for r in pick) + [n_rows - 1], keep_chains
+
+
+def write_outputs(directory, arrays, rows, rank, world):
+    """DIR/<name>.npy of one rank's outputs (<name>.rank<r>.npy for the
+    other ranks of an N > 1 job); returns the line's description of them."""
+    os.makedirs(directory, exist_ok=True)
+    desc = {}
+    for name, arr in arrays.items():
+        fname = f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"
+        np.save(os.path.join(directory, fname), arr)
+        desc[name] = {"file": fname, "shape": list(arr.shape), "dtype": str(arr.dtype)}
+    desc["positions"]["rows"] = rows
+    desc["positions"]["layout"] = "[row, chain, dim]: the listed transitions of the timed call, the leading " \
+                                  f"chains of rank {rank} of {world}"
+    return desc
+
+
 def fin(v):
     """float, or None where undefined (diagnostics need >= 4 draws)."""
     v = float(v)
@@ -765,6 +830,62 @@ LEG_NOTES = {
 }
 
 
+def full_measurements(a, be, cp, comm, sampler, ds, x0, offset, lanes, elems):
+    """Everything --full measures after the headline's timed region, in the
+    order it always ran: the diagnostics of the timed draws, the ESS legs,
+    the other BASELINE configs, then rank 0's own measurements (the other
+    ranks wait at main()'s closing barrier). Returns this rank's figures."""
+    from general_mcmc_amd.distributed import shard
+    world, rank, D = cp.world, cp.rank, a.dim
+    # diagnostics of the timed draws (device; RCCL all-gather when N > 1)
+    td0 = time.perf_counter()
+    if a.steps >= 4:
+        rhat, ess = be.diagnostics(ds, comm)
+    else:
+        rhat = ess = np.full(D, np.nan, dtype=np.float32)
+    t_diag = time.perf_counter() - td0
+
+    # ESS legs on their own schedules (every rank; diagnostics over all chains)
+    legs = {}
+    for name, nd, nc in (("cfg2_schedule", a.ess_discard, a.ess_collect),
+                         ("long", a.ess_long_discard, a.ess_long_collect)):
+        if nc < 4 or (name == "long" and nd <= 0):
+            continue
+        ts, tdg, rh, es = be.ess_leg(x0, offset, comm, nd, nc)
+        ts, tdg = cp.max([ts, tdg])
+        legs[name] = {"n_discard": nd, "n_collect": nc, "sampling_s": float(ts), "diag_s": float(tdg),
+                      "ess_mean": fin(np.mean(es)), "ess_min": fin(np.min(es)),
+                      "ess_per_sec_sampling": fin(np.mean(es) / ts),
+                      "ess_min_per_sec_sampling": fin(np.min(es) / ts),
+                      "ess_per_sec_end_to_end": fin(np.mean(es) / (ts + tdg)),
+                      "rhat": rhat_block(rh)}
+    # the other BASELINE configs (every rank, its share; diagnostics over all)
+    configs = {}
+    for name in [c for c in a.configs.split(",") if c]:
+        cfg = CONFIG_LEGS[name]
+        off, _ = shard(cfg["chains"] * world, world, rank)
+        figs = be.config_leg(name, cfg, off, comm)
+        rh, es = figs.pop("rhat"), figs.pop("ess")
+        configs[name] = config_summary(name, cfg, cp.gather(figs), world, rh, es)
+    comm_info = comm.info() if comm is not None else None
+
+    # rank-0-only measurements; the other ranks wait at the closing barrier
+    extra = {}
+    if rank == 0:
+        extra["copy_ceiling_gbs"] = be.copy_ceiling()
+        extra["per_leapfrog_hbm"] = be.per_leapfrog_hbm()
+        extra["host_output"] = be.host_output(sampler)
+        extra["north_star_check"] = be.north_star_check(offset=offset) if a.north_star else None
+        extra["cpu_baseline"] = be.cpu_baseline(x0, lanes, elems) if a.cpu_seconds > 0 else None
+        if a.cpu_config_seconds > 0:
+            threads = a.cpu_threads or available_cores()[0]
+            for name in configs:
+                configs[name]["cpu_baseline"] = config_cpu_baseline(name, CONFIG_LEGS[name], threads,
+                                                                    a.cpu_config_seconds)
+    return {"rhat": rhat, "ess": ess, "diag_s": t_diag, "legs": legs, "configs": configs,
+            "comm_info": comm_info, "extra": extra}
+
+
 def pin_host_thread(rank: int, world: int):
     """A single rank's host thread on the CPU it runs on, from the device
     warm-up to the end of the timed region, so that the timed call's launch
@@ -814,8 +935,10 @@ def main(argv=None, backend=None):
     if hasattr(sampler, "set_async"):
         sampler.set_async(True)
     lanes, elems = sampler.layout()
-    comm = be.comm()
-    if world > 1 and (comm is None or comm.info()["nranks"] != world):
+    # the RCCL communicator serves the diagnostics of --full only: the timed
+    # region itself has no collective (the control plane's barriers are gloo)
+    comm = be.comm() if a.full else None
+    if a.full and world > 1 and (comm is None or comm.info()["nranks"] != world):
         raise SystemExit(f"bench.py: the RCCL communicator does not span the {world} ranks")
 
     def barrier_sync():
@@ -863,51 +986,13 @@ def main(argv=None, backend=None):
     kmax = max(r["kernel_ms"] for r in ranks)
     launch_ms = max(r["kernel_ms"] / max(r["launches"], 1) for r in ranks)
 
-    # diagnostics of the timed draws (device; RCCL all-gather when N > 1)
-    td0 = time.perf_counter()
-    if a.steps >= 4:
-        rhat, ess = be.diagnostics(ds, comm)
-    else:
-        rhat = ess = np.full(D, np.nan, dtype=np.float32)
-    t_diag = time.perf_counter() - td0
-
-    # ESS legs on their own schedules (every rank; diagnostics over all chains)
-    legs = {}
-    for name, nd, nc in (("cfg2_schedule", a.ess_discard, a.ess_collect),
-                         ("long", a.ess_long_discard, a.ess_long_collect)):
-        if nc < 4 or (name == "long" and nd <= 0):
-            continue
-        ts, tdg, rh, es = be.ess_leg(x0, offset, comm, nd, nc)
-        ts, tdg = cp.max([ts, tdg])
-        legs[name] = {"n_discard": nd, "n_collect": nc, "sampling_s": float(ts), "diag_s": float(tdg),
-                      "ess_mean": fin(np.mean(es)), "ess_min": fin(np.min(es)),
-                      "ess_per_sec_sampling": fin(np.mean(es) / ts),
-                      "ess_min_per_sec_sampling": fin(np.min(es) / ts),
-                      "ess_per_sec_end_to_end": fin(np.mean(es) / (ts + tdg)),
-                      "rhat": rhat_block(rh)}
-    # the other BASELINE configs (every rank, its share; diagnostics over all)
-    configs = {}
-    for name in [c for c in a.configs.split(",") if c]:
-        cfg = CONFIG_LEGS[name]
-        off, _ = shard(cfg["chains"] * world, world, rank)
-        figs = be.config_leg(name, cfg, off, comm)
-        rh, es = figs.pop("rhat"), figs.pop("ess")
-        configs[name] = config_summary(name, cfg, cp.gather(figs), world, rh, es)
-    comm_info = comm.info() if comm is not None else None
-
-    # rank-0-only measurements; the other ranks wait at the closing barrier
-    extra = {}
-    if rank == 0:
-        extra["copy_ceiling_gbs"] = be.copy_ceiling()
-        extra["per_leapfrog_hbm"] = be.per_leapfrog_hbm()
-        extra["host_output"] = be.host_output(sampler)
-        extra["north_star_check"] = be.north_star_check(offset=offset) if a.north_star else None
-        extra["cpu_baseline"] = be.cpu_baseline(x0, lanes, elems) if a.cpu_seconds > 0 else None
-        if a.cpu_config_seconds > 0:
-            threads = a.cpu_threads or available_cores()[0]
-            for name in configs:
-                configs[name]["cpu_baseline"] = config_cpu_baseline(name, CONFIG_LEGS[name], threads,
-                                                                    a.cpu_config_seconds)
+    # what the timed call returned, written out after the clock has stopped
+    # (the draws stay valid until the sampler's next run, which --full starts)
+    outputs = None
+    if a.dump_outputs:
+        arrays, rows = be.outputs(sampler, ds)
+        outputs = write_outputs(a.dump_outputs, arrays, rows, rank, world)
+    full = full_measurements(a, be, cp, comm, sampler, ds, x0, offset, lanes, elems) if a.full else None
     cp.barrier()
 
     line = None
@@ -918,7 +1003,9 @@ def main(argv=None, backend=None):
         achieved_tf = fa * C_loc * L * steps_per_launch / (launch_ms * 1e-3) / 1e12
         hbm_bytes = b_step(D, L, s_bytes) * C_loc * steps_per_launch
         hbm_gbs = hbm_bytes / (launch_ms * 1e-3) / 1e9
-        traffic, issue = load_pmc(C_loc, D, L, a.dtype, a.steps)
+        extra = full["extra"] if full else {}
+        # the profiled launch's counters (a stored file) belong to --full's roofline detail
+        traffic, issue = load_pmc(C_loc, D, L, a.dtype, a.steps) if full else (None, None)
         line = {
             "metric": METRIC,
             "value": value,
@@ -943,12 +1030,7 @@ def main(argv=None, backend=None):
                                         "the W warm-up transitions of the measured sampler",
                        "note": "wall = barrier-bracketed timed region (max over ranks); kernel = HIP events "
                                "around the run's launches on the sampler's stream; host_overhead = wall - kernel"},
-            "ess_per_sec": legs.get("cfg2_schedule", {}).get("ess_per_sec_sampling"),
-            "ess": legs,
-            "timed_draws_diagnostics": {"ess_mean": fin(np.mean(ess)), "ess_min": fin(np.min(ess)),
-                                        "rhat": rhat_block(rhat), "diag_s": t_diag,
-                                        "note": "the --steps draws of the timed region, started "
-                                                "--warmup transitions from N(0,1): not a mixing figure"},
+            "full": bool(a.full),
             "roofline": {"bound": "valu", "achieved": achieved_tf, "peak": VALU_F32_PEAK_TFLOPS,
                          "unit": "TFLOP/s", "frac": achieved_tf / VALU_F32_PEAK_TFLOPS,
                          "traffic": traffic["bytes"] if traffic else None,
@@ -971,13 +1053,25 @@ def main(argv=None, backend=None):
                                                     "roofline fraction"},
                          "copy_ceiling_gbs": extra.get("copy_ceiling_gbs"),
                          "per_leapfrog_hbm": extra.get("per_leapfrog_hbm")},
-            "cpu_baseline": extra.get("cpu_baseline"),
-            "configs": configs,
-            "rccl": comm_info,
-            "north_star_check": extra.get("north_star_check"),
-            "host_output": extra.get("host_output"),
             "build": _build_info(),
         }
+        if outputs is not None:
+            line["outputs"] = outputs
+        if full:
+            legs, ess = full["legs"], full["ess"]
+            line.update({
+                "ess_per_sec": legs.get("cfg2_schedule", {}).get("ess_per_sec_sampling"),
+                "ess": legs,
+                "timed_draws_diagnostics": {"ess_mean": fin(np.mean(ess)), "ess_min": fin(np.min(ess)),
+                                            "rhat": rhat_block(full["rhat"]), "diag_s": full["diag_s"],
+                                            "note": "the --steps draws of the timed region, started "
+                                                    "--warmup transitions from N(0,1): not a mixing figure"},
+                "cpu_baseline": extra.get("cpu_baseline"),
+                "configs": full["configs"],
+                "rccl": full["comm_info"],
+                "north_star_check": extra.get("north_star_check"),
+                "host_output": extra.get("host_output"),
+            })
         print(json.dumps(line), flush=True)
     if comm is not None:
         comm.close()

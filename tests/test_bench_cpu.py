@@ -11,8 +11,9 @@ import numpy as np
 import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGV = ["--steps", "8", "--warmup", "2", "--chains", "128", "--cpu-seconds", "0.05", "--cpu-config-seconds", "0.05",
-        "--ess-discard", "4", "--ess-collect", "8", "--ess-long-discard", "4", "--ess-long-collect", "8"]
+PLAIN = ["--steps", "8", "--warmup", "2", "--chains", "128"]
+ARGV = PLAIN + ["--full", "--cpu-seconds", "0.05", "--cpu-config-seconds", "0.05",
+                "--ess-discard", "4", "--ess-collect", "8", "--ess-long-discard", "4", "--ess-long-collect", "8"]
 
 
 def _free_port():
@@ -77,6 +78,11 @@ def stub_backend():
 
         def comm(self):
             return _Comm(self.cp) if self.cp.world > 1 else None
+
+        def outputs(self, sampler, ds):
+            rows, n_chains = bench.dump_sample(ds.n_collect, ds.n_chains, ds.dim, 4)
+            pos = np.arange(len(rows) * n_chains * ds.dim, dtype=np.float32).reshape(len(rows), n_chains, ds.dim)
+            return {"positions": pos, "accept_counts": np.full(ds.n_chains, 3.0)}, rows
 
         def diagnostics(self, ds, comm):
             return np.full(ds.dim, 0.99, np.float32), np.full(ds.dim, 100.0 * ds.n_chains, np.float32)
@@ -157,6 +163,54 @@ def test_bench_cli_rank_count_mismatch_fails():
     r = _cli(ARGV + ["--gpus", "2"], extra_env={"WORLD_SIZE": "1"})
     assert r.returncode != 0
     assert "--gpus 2" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """Without --full the run is set-up, warm-up, the timed transitions and
+    the line: none of the legs behind --full starts (the stub's would succeed,
+    so each is made to fail here), the headline fields keep their meaning,
+    and --dump-outputs writes the timed call's arrays."""
+    import bench
+
+    class Plain(stub_backend()):
+        def _not_plain(self, *a, **k):
+            raise AssertionError("a --full measurement ran in a plain run")
+
+        comm = diagnostics = ess_leg = copy_ceiling = per_leapfrog_hbm = host_output = _not_plain
+        north_star_check = config_leg = cpu_baseline = _not_plain
+
+    env = {k: os.environ.pop(k) for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK") if k in os.environ}
+    try:
+        line = bench.main(PLAIN + ["--gpus", "1", "--dump-outputs", str(tmp_path / "out")], backend=Plain)
+    finally:
+        os.environ.update(env)
+    assert line["full"] is False and line["steps"] == 8 and line["warmup"] == 2
+    assert line["metric"] == bench.METRIC and line["unit"] == "chain-leapfrog steps/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32"
+    wall = line["timing"]["wall_ms"]
+    assert line["ms_per_step"] == wall / 8 and line["value"] == 128 * 50 * 8 / (wall * 1e-3)
+    assert line["roofline"]["launch_ms"] == 1.0 and line["roofline"]["frac"] > 0
+    for key in ("ess", "configs", "cpu_baseline", "host_output", "north_star_check", "timed_draws_diagnostics"):
+        assert key not in line
+    pos = np.load(tmp_path / "out" / "positions.npy")
+    acc = np.load(tmp_path / "out" / "accept_counts.npy")
+    assert pos.dtype == np.float32 and pos.shape == (8, 128, 64) and acc.dtype == np.float64 and acc.shape == (128,)
+    assert line["outputs"]["positions"]["rows"] == list(range(8))
+    assert line["outputs"]["positions"]["shape"] == [8, 128, 64]
+
+
+def test_dump_sample_stays_within_budget_and_keeps_the_last_row():
+    import bench
+    for n_rows, n_chains, dim, size in ((100, 4096, 64, 4), (20, 4096, 64, 4), (1, 16, 3, 8), (5000, 65536, 128, 8),
+                                        (3, 1 << 22, 64, 4)):
+        rows, keep = bench.dump_sample(n_rows, n_chains, dim, size)
+        assert rows == sorted(set(rows)) and rows[-1] == n_rows - 1 and rows[0] >= 0
+        assert 1 <= keep <= n_chains and len(rows) * keep * dim * size <= bench.DUMP_BUDGET_BYTES
+        assert (rows, keep) == bench.dump_sample(n_rows, n_chains, dim, size)  # seeded: the same every time
+        if n_rows * n_chains * dim * size <= bench.DUMP_BUDGET_BYTES:
+            assert rows == list(range(n_rows)) and keep == n_chains
+        # positions.npy and accept_counts.npy (8 bytes per kept chain) together, headers aside
+        assert len(rows) * keep * dim * size + 8 * keep < 63e6
 
 
 def _keys(d, prefix=""):

@@ -42,10 +42,10 @@ for step in "$@"; do
     warmup) run warmup_probe 300 python tools/probe_warmup.py ;;
     hostpath) run host_path 120 python tools/probe_host_path.py ;;
     steptests) run step_tests 300 python -u -m pytest tests/test_gpu_step.py -x -v --timeout 120 --timeout-method thread ;;
-    benchn) run bench_new 600 python bench.py --steps 20 --warmup 5 ;;
+    benchn) run bench_new 600 python bench.py --full --steps 20 --warmup 5 ;;
     smoke) run smoke 120 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench20) run bench20 300 python bench.py --steps 20 --warmup 5 ;;
-    bench) run bench 300 python bench.py ;;
+    bench20) run bench20 300 python bench.py --full --steps 20 --warmup 5 ;;
+    bench) run bench 300 python bench.py --full ;;
     configs) run configs 300 python tools/bench_configs.py ;;
     mfma64) run mfma_f64_probe 60 ./tools/probes/bin/mfma_f64_probe ;;
     first)

@@ -4,7 +4,7 @@
 # region off), reduced to cycles / duration for the timed hmc_kernel dispatch.
 source tools/gpu_check.sh
 O=gpurun_out/hclock
-ARGS="--steps 20 --warmup 5 --cpu-seconds 0 --cpu-config-seconds 0 --ess-long-discard 0 --no-north-star"
+ARGS="--full --steps 20 --warmup 5 --cpu-seconds 0 --cpu-config-seconds 0 --ess-long-discard 0 --no-north-star"
 run hclock_trace 200 rocprofv3 --kernel-trace -d $O/trace -o run --output-format csv -- python3 bench.py $ARGS &&
 run hclock_grbm 200 timeout -s KILL 180 rocprofv3 --pmc GRBM_GUI_ACTIVE -d $O/grbm -o run --output-format csv -- python3 bench.py $ARGS &&
 python3 - <<'PY' > gpurun_out/hclock.json

@@ -14,7 +14,7 @@ source tools/gpu_check.sh
 K=${K:-20}
 W=${W:-5}
 O=gpurun_out/prof_r06_K$K
-ARGS="--steps $K --warmup $W --cpu-seconds 0 --cpu-config-seconds 0 --ess-long-discard 0 --no-north-star"
+ARGS="--full --steps $K --warmup $W --cpu-seconds 0 --cpu-config-seconds 0 --ess-long-discard 0 --no-north-star"
 run prof_trace_$K 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py $ARGS &&
 run prof_fetch_$K 300 timeout -s KILL 280 rocprofv3 --pmc FETCH_SIZE -d $O/fetch -o run --output-format csv -- python3 bench.py $ARGS &&
 run prof_write_$K 300 timeout -s KILL 280 rocprofv3 --pmc WRITE_SIZE -d $O/write -o run --output-format csv -- python3 bench.py $ARGS &&
