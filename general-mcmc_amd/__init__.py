@@ -10,7 +10,7 @@ from ._lib import GMError
 from .core import init, init_det, init_with_seed
 from .distributions import (CustomTarget, DenseGaussian, DiffableGaussian2D, Gaussian2D,
                             IsotropicGaussian, Rosenbrock2D, RosenbrockND)
-from .hmc import HMC
+from .hmc import HMC, HMCAdaptConfig
 from .metropolis_hastings import MetropolisHastings
 from .nuts import NUTS, MassMatrix, NUTSChain, NUTSMassMatrixConfig
 from .stats import (BasicStats, ChainStats, MultiChainTracker, Progress, RunStats, basic_stats,
@@ -22,4 +22,5 @@ __all__ = [
     "init_det",
     "init_with_seed", "split_rhat_mean_ess", "basic_stats", "BasicStats", "RunStats", "GMError",
     "batch_vector", "MultiChainTracker", "ChainStats", "Progress", "NUTSMassMatrixConfig", "MassMatrix",
+    "HMCAdaptConfig",
 ]

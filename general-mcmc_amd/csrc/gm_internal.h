@@ -69,6 +69,14 @@ hipError_t with_events(LaunchEvents ev, hipStream_t st, F&& launch) {
 // ---- HMC -------------------------------------------------------------------
 hipError_t launch_hmc(gm_dtype dt, const TargetDev& tg, const Layout& lay, const HmcLaunch& a,
                       hipStream_t st, LaunchEvents ev = {});
+// per-chain step sizes / diagonal metric / warm-up (hmc_adapt_kernels.hip);
+// mode: 0 frozen, 1 step-size adaptation, 2 step size + Welford statistics
+hipError_t launch_hmc_adapt(gm_dtype dt, const TargetDev& tg, const Layout& lay, const HmcAdaptLaunch& a,
+                            int mode, hipStream_t st, LaunchEvents ev = {});
+// a warm-up window's end (rn >= 5): metric from the Welford state, restart of the dual averaging
+hipError_t launch_hmc_adapt_window(gm_dtype dt, long long C, int D, double regularize, double jitter,
+                                   long long rn, void* eps, const void* eps_bar, void* h_bar, void* mu,
+                                   void* dinv, void* dsq, void* rmean, void* rm2, hipStream_t st);
 
 // ---- run_progress statistics (gm_track.h, tracker_kernels.hip) -------------
 // ChainTracker::new for every chain from the current positions

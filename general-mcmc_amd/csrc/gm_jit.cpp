@@ -15,8 +15,14 @@ namespace gm {
 
 namespace {
 
-const char* kKernelHeader[] = {"hmc_device.h", "mh_device.h", "nuts_device.h", "util_device.h"};
-const char* kKernelName[] = {"hmc_kernel", "mh_kernel", "nuts_kernel", "logp_grad_kernel"};
+const char* kKernelHeader[] = {"hmc_device.h", "mh_device.h", "nuts_device.h", "util_device.h",
+                               "hmc_adapt_device.h", "hmc_adapt_device.h", "hmc_adapt_device.h"};
+const char* kKernelName[] = {"hmc_kernel", "mh_kernel", "nuts_kernel", "logp_grad_kernel",
+                             "hmc_adapt_kernel", "hmc_adapt_kernel", "hmc_adapt_kernel"};
+// the kernel's trailing template argument, if any: the NUTS metric handling
+// (user targets run with or without mass-matrix adaptation from one module),
+// the MODE of hmc_adapt_kernel
+const char* kKernelTail[] = {"", "", ", 2", "", ", 0", ", 1", ", 2"};
 
 // The adapter between the user's function and the engine's target concept
 // (bind / lds_bytes / eval, gm_device.h): one chain per lane, so E = dim and
@@ -66,10 +72,8 @@ std::string program_source(JitKernel which, const char* src, int D) {
 
 std::string name_expr(JitKernel which, gm_dtype dt, int D) {
   const char* t = dt == GM_F32 ? "float" : "double";
-  // the NUTS kernel's last argument: metric handling compiled in (user
-  // targets run with or without mass-matrix adaptation from one module)
   return std::string("gm::") + kKernelName[which] + "<" + t + ", 1, " + std::to_string(D) +
-         ", gm::UserTarget<" + t + ">" + (which == JIT_NUTS ? ", 2" : "") + " >";
+         ", gm::UserTarget<" + t + ">" + kKernelTail[which] + " >";
 }
 
 // compile; on success fills code and the lowered kernel name

@@ -6,7 +6,7 @@
 //     template <class T> __device__ T gm_logp_grad(const T* x, T* g, const T* params);
 // for one chain's position x[GM_DIM] (GM_DIM is a macro), writing the gradient
 // to g and returning the log-density. gm_jit.cpp compiles the engine's own
-// sampler kernels (hmc_device.h, mh_device.h, nuts_device.h, util_device.h)
+// sampler kernels (hmc_device.h, hmc_adapt_device.h, mh_device.h, nuts_device.h, util_device.h)
 // around it for the one-chain-per-lane layout (lanes 1, elems = dim), with
 // the same flags as the ahead-of-time build, and caches the code per process.
 #pragma once
@@ -21,7 +21,16 @@ struct JitHeader {
 extern const JitHeader jit_headers[];  // embedded device headers (build/gm_jit_headers.cpp)
 extern const int n_jit_headers;
 
-enum JitKernel { JIT_HMC = 0, JIT_MH = 1, JIT_NUTS = 2, JIT_LOGP = 3 };
+enum JitKernel {
+  JIT_HMC = 0,
+  JIT_MH = 1,
+  JIT_NUTS = 2,
+  JIT_LOGP = 3,
+  // hmc_adapt_kernel (hmc_adapt_device.h), MODE 0, 1, 2
+  JIT_HMC_ADAPT0 = 4,
+  JIT_HMC_ADAPT1 = 5,
+  JIT_HMC_ADAPT2 = 6
+};
 
 // Host mirror of the device adapter gm::UserTarget<T> (kernel argument).
 struct UserTargetArg {

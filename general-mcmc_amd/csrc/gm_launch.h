@@ -37,6 +37,27 @@ struct HmcLaunch {
   void* zs = nullptr;           // wide layouts: momentum block scratch [C][S][lanes*elems]
 };
 
+// ---- HMC with per-chain step sizes and a diagonal metric --------------------
+// (hmc_adapt_device.h). A launch is wholly frozen (MODE 0) or wholly warm-up
+// (MODE 1 step size, MODE 2 step size + Welford statistics): the host cuts
+// launches at the warm-up's end and at every window end.
+struct HmcAdaptLaunch {
+  HmcLaunch h;                  // as for the plain kernel (h.eps and h.zs unused)
+  void* eps = nullptr;          // [C] per-chain step size, in/out while adapting
+  void* eps_bar = nullptr;      // [C] in/out (MODE >= 1)
+  void* h_bar = nullptr;        // [C] in/out (MODE >= 1)
+  const void* mu = nullptr;     // [C]
+  const void* dinv = nullptr;   // [C][D] M^-1
+  const void* dsq = nullptr;    // [C][D] sqrt(M) = 1/sqrt(dinv)
+  void* rmean = nullptr;        // [C][D] Welford mean, in/out (MODE 2)
+  void* rm2 = nullptr;          // [C][D] Welford sum of squared deviations, in/out (MODE 2)
+  double delta = 0.8;           // target acceptance
+  long long k0 = 0;             // dual-averaging restart counter before this launch
+  long long rn0 = 0;            // Welford count before this launch
+  long long m0 = 0;             // warm-up transitions before this launch (m = m0 + s + 1)
+  long long sb = 0, lim = 0;    // Welford collects while sb < m < lim (lim = n_discard - end_buffer)
+};
+
 // ---- MH --------------------------------------------------------------------
 struct MhLaunch {
   void* q = nullptr;

@@ -182,6 +182,24 @@ struct RoctxRange {
   }
 };
 
+// HMC with per-chain step sizes, a diagonal metric and their warm-up
+// (gm_hmc_set_*; hmc_adapt_device.h). `has`: the per-chain arrays exist and
+// the sampler runs hmc_adapt_kernel instead of hmc_kernel.
+struct HmcAdapt {
+  bool has = false;
+  int mode = 0;        // 0 none, 1 step size, 2 step size + diagonal metric
+  bool armed = false;  // the next run's n_discard transitions are the warm-up
+  double delta = 0.8;
+  long long sb = 0, eb = 0, iw = 0;
+  double reg = 0, jit = 0;
+  // dual-averaging restart counter and Welford count: the window schedule
+  // depends on the transition index only, so they are the same for every chain
+  long long k = 0, rn = 0;
+  long long pending_warm = 0;  // n_discard of the gm_run* call that is entering run_steps
+  void *eps = nullptr, *eps_bar = nullptr, *h_bar = nullptr, *mu = nullptr;       // [C]
+  void *dinv = nullptr, *dsq = nullptr, *rmean = nullptr, *rm2 = nullptr;         // [C][D]
+};
+
 struct gm_sampler {
   int kind = 0;
   gm_dtype dt = GM_F32;
@@ -226,6 +244,7 @@ struct gm_sampler {
   long long total_steps = 0;  // transitions since creation
   long long last_rows = 0;    // sample rows produced by the last run
   NutsState nuts;
+  HmcAdapt ha;
   // run_progress statistics: per-chain trackers (MH, NUTS) and a
   // MultiChainTracker (HMC), one allocation each (TrackSet)
   void* d_trk = nullptr;
@@ -301,6 +320,101 @@ static int upload_as(gm_dtype dt, const double* src, size_t n, void** dst) {
   }
   GM_HIP(hipMalloc(dst, n * esz));
   GM_HIP(hipMemcpy(*dst, tmp.data(), n * esz, hipMemcpyHostToDevice));
+  return GM_OK;
+}
+
+// double host values <-> a device array of the sampler dtype
+static int put_as(gm_dtype dt, const double* src, size_t n, void* dst) {
+  if (dt == GM_F64) {
+    GM_HIP(hipMemcpy(dst, src, n * 8, hipMemcpyHostToDevice));
+    return GM_OK;
+  }
+  std::vector<float> tmp(n);
+  for (size_t i = 0; i < n; ++i) tmp[i] = (float)src[i];
+  GM_HIP(hipMemcpy(dst, tmp.data(), n * 4, hipMemcpyHostToDevice));
+  return GM_OK;
+}
+static int get_as(gm_dtype dt, const void* src, size_t n, double* dst) {
+  if (dt == GM_F64) {
+    GM_HIP(hipMemcpy(dst, src, n * 8, hipMemcpyDeviceToHost));
+    return GM_OK;
+  }
+  std::vector<float> tmp(n);
+  GM_HIP(hipMemcpy(tmp.data(), src, n * 4, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i) dst[i] = (double)tmp[i];
+  return GM_OK;
+}
+
+// ---- HMC per-chain step sizes / metric state (HmcAdapt) --------------------
+static void hmc_adapt_free(gm_sampler* s) {
+  HmcAdapt& h = s->ha;
+  for (void** p : {&h.eps, &h.eps_bar, &h.h_bar, &h.mu, &h.dinv, &h.dsq, &h.rmean, &h.rm2}) {
+    if (*p) hipFree(*p);
+    *p = nullptr;
+  }
+  h = HmcAdapt();
+}
+
+// the step size the kernels use for a chain without per-chain state
+static double hmc_eps_rounded(const gm_sampler* s) { return s->dt == GM_F32 ? (double)(float)s->eps : s->eps; }
+
+// Allocates the per-chain arrays in their start state: every step size the
+// creation value, the identity metric, no statistics. From here on the sampler
+// runs hmc_adapt_kernel.
+static int hmc_adapt_ensure(gm_sampler* s) {
+  HmcAdapt& h = s->ha;
+  if (h.has) return GM_OK;
+  if (s->tg.kind == GM_TARGET_CUSTOM) {  // a source that does not compile for this kernel fails here
+    const int rc = jit_prepare(JIT_HMC_ADAPT0, s->dt, s->tg);
+    if (rc) return rc;
+  }
+  const size_t C = (size_t)s->C, CD = C * (size_t)s->D;
+  hipError_t e = hipSuccess;
+  for (void** p : {&h.eps, &h.eps_bar, &h.h_bar, &h.mu})
+    if (e == hipSuccess) e = hipMalloc(p, C * s->esz);
+  for (void** p : {&h.dinv, &h.dsq, &h.rmean, &h.rm2})
+    if (e == hipSuccess) e = hipMalloc(p, CD * s->esz);
+  if (e != hipSuccess) {
+    hmc_adapt_free(s);
+    set_error(std::string("per-chain HMC state allocation failed: ") + hipGetErrorString(e));
+    return GM_ENOMEM;
+  }
+  std::vector<double> v(CD > C ? CD : C, 1.0);
+  int rc = put_as(s->dt, v.data(), CD, h.dinv);
+  if (!rc) rc = put_as(s->dt, v.data(), CD, h.dsq);
+  std::fill(v.begin(), v.end(), s->eps);
+  if (!rc) rc = put_as(s->dt, v.data(), C, h.eps);
+  if (!rc) rc = put_as(s->dt, v.data(), C, h.eps_bar);
+  if (!rc) {
+    e = hipMemset(h.h_bar, 0, C * s->esz);
+    if (e == hipSuccess) e = hipMemset(h.mu, 0, C * s->esz);
+    if (e == hipSuccess) e = hipMemset(h.rmean, 0, CD * s->esz);
+    if (e == hipSuccess) e = hipMemset(h.rm2, 0, CD * s->esz);
+    if (e != hipSuccess) {
+      set_error(std::string("per-chain HMC state setup failed: ") + hipGetErrorString(e));
+      rc = GM_EHIP;
+    }
+  }
+  if (rc) {
+    const std::string msg = gm_last_error();
+    hmc_adapt_free(s);
+    set_error(msg);
+    return rc;
+  }
+  h.has = true;
+  return GM_OK;
+}
+
+// The gm_hmc_set_* / gm_hmc_get_* calls need an HMC sampler (GM_ESTATE) on a
+// lane-group layout (GM_EINVAL on the wide path of dim > 1024).
+static int hmc_adapt_callable(gm_sampler* s) {
+  GM_REQ(s, "sampler is NULL");
+  if (s->kind != K_HMC) {
+    set_error("per-chain step sizes, the diagonal metric and their warm-up are for HMC samplers");
+    return GM_ESTATE;
+  }
+  GM_REQ(s->D <= 1024 && !layout_is_wide(s->lay),
+         "per-chain step sizes, the diagonal metric and their warm-up do not take wide layouts (dim > 1024)");
   return GM_OK;
 }
 
@@ -393,8 +507,10 @@ int gm_custom_target_check(const char* source, gm_dtype dtype, int64_t dim, int3
   GM_REQ(source, "source is NULL");
   GM_REQ(dtype == GM_F32 || dtype == GM_F64, "bad dtype");
   GM_REQ(dim >= 1 && dim <= GM_CUSTOM_MAX_DIM, "CUSTOM targets support dim in [1, 256]");
-  GM_REQ(kind >= 0 && kind <= 3, "kind: 0 logp/grad, 1 HMC, 2 MH, 3 NUTS");
-  const JitKernel jk = kind == 1 ? JIT_HMC : kind == 2 ? JIT_MH : kind == 3 ? JIT_NUTS : JIT_LOGP;
+  GM_REQ(kind >= 0 && kind <= 4, "kind: 0 logp/grad, 1 HMC, 2 MH, 3 NUTS, 4 HMC warm-up");
+  // 4: hmc_adapt_kernel in its most general instantiation (MODE 2)
+  const JitKernel jk = kind == 1 ? JIT_HMC : kind == 2 ? JIT_MH : kind == 3 ? JIT_NUTS
+                       : kind == 4 ? JIT_HMC_ADAPT2 : JIT_LOGP;
   return jit_compile(jk, dtype, source, (int)dim);
 }
 
@@ -653,6 +769,7 @@ int gm_sampler_set_layout(gm_sampler* s, int32_t lanes, int32_t elems) {
            "layout (lanes, elems) is not compiled in");
     GM_REQ(!wide || s->kind == K_HMC, "wide layouts (lanes > 64) are for the HMC and NUTS samplers");
   }
+  GM_REQ(!(wide && s->ha.has), "per-chain step sizes / metric (gm_hmc_set_*) do not take wide layouts");
   GM_REQ((long long)lanes * elems >= s->D, "lanes*elems must cover dim");
   GM_REQ((long long)lanes * elems < 2LL * s->D || lanes == 1 ||
              ((long long)(lanes / 2) * elems < s->D),
@@ -754,9 +871,16 @@ static int ensure_run_events(gm_sampler* s) {
 
 // Runs `total` transitions; transitions with index >= collect_from (0-based
 // within this call) are stored at sample rows (index - collect_from).
+static int run_hmc_adapt(gm_sampler* s, long long total, long long collect_from, const StepHook* hook,
+                         long long chunk, int lf_unroll, long long warm);
+
 static int run_steps(gm_sampler* s, long long total, long long collect_from, int progress,
                      const TrackLaunch* trk = nullptr, const StepHook* hook = nullptr,
                      long long chunk_override = 0) {
+  // the n_discard of a gm_run* call, consumed here: gm_step and the
+  // collection part of run_progress never start a warm-up
+  const long long pending_warm = s->ha.pending_warm;
+  s->ha.pending_warm = 0;
   GM_HIP(use_device(s->device));
   s->last_ms = 0;
   s->last_launches = 0;
@@ -776,6 +900,10 @@ static int run_steps(gm_sampler* s, long long total, long long collect_from, int
   if (rc) return rc;
   const int lf_unroll = s->kind != K_HMC ? 1 : s->lf_unroll ? s->lf_unroll
                                                              : hmc_lf_unroll((s->C * s->lay.lanes + 63) / 64);
+  if (s->kind == K_HMC && s->ha.has) {
+    const long long warm = s->ha.armed && s->ha.mode ? std::min(pending_warm, total) : 0;
+    return run_hmc_adapt(s, total, collect_from, hook, chunk, lf_unroll, warm);
+  }
   for (long long start = 0; start < total; start += chunk) {
     LaunchEvents ev;  // start with the first launch, stop with the last
     if (start == 0) ev.start = s->evs[0];
@@ -849,6 +977,118 @@ static int run_steps(gm_sampler* s, long long total, long long collect_from, int
   return GM_OK;
 }
 
+// The HMC run of a sampler with per-chain step sizes / metric: the first
+// `warm` transitions are the warm-up (MODE 1 or 2 launches, cut at every
+// window end, where hmc_adapt_window_kernel runs on the stream, and at the
+// warm-up's end, where eps = eps_bar), the rest frozen (MODE 0). Nothing here
+// waits for the device, so asynchronous runs stay asynchronous.
+static int run_hmc_adapt(gm_sampler* s, long long total, long long collect_from, const StepHook* hook,
+                         long long chunk, int lf_unroll, long long warm) {
+  HmcAdapt& h = s->ha;
+  // window ends of the NUTS schedule (nuts_run / nuts_set_mass), by transition index m
+  std::vector<long long> wends;
+  const long long lim = warm > h.eb ? warm - h.eb : 0;
+  if (warm > 0 && h.mode == 2) {
+    long long sched_len = h.iw > 10 ? h.iw : 10;
+    long long sched_next = (h.sb > 1 ? h.sb : 1) + sched_len;
+    for (long long m = 1; m <= warm; ++m) {
+      if (m <= h.sb || !(m < lim)) continue;
+      if (m >= sched_next || m + 1 >= lim) {
+        sched_next += sched_len;
+        sched_len = sched_len * 2 < 400 ? sched_len * 2 : 400;
+        wends.push_back(m);
+      }
+    }
+  }
+  size_t wi = 0;
+  long long n_launch = 0;
+  for (long long pos = 0; pos < total;) {
+    long long n = total - pos < chunk ? total - pos : chunk;
+    const bool in_warm = pos < warm;
+    bool upd = false;
+    if (in_warm) {
+      if (n > warm - pos) n = warm - pos;
+      if (wi < wends.size() && wends[wi] <= pos + n) {  // cut at the window end (transition m = pos + n)
+        n = wends[wi] - pos;
+        upd = true;
+        ++wi;
+      }
+    }
+    LaunchEvents ev;
+    if (pos == 0) ev.start = s->evs[0];
+    if (pos + n >= total) ev.stop = s->evs[1];
+    long long cf = collect_from - pos;
+    if (cf < 0) cf = 0;
+    if (cf > n) cf = n;
+    long long row0 = pos - collect_from;
+    if (row0 < 0) row0 = 0;
+    HmcAdaptLaunch a;
+    a.h.q = s->d_q;
+    a.h.logp = s->d_logp;
+    a.h.accepts = s->d_acc;
+    a.h.samples = s->d_samples;
+    a.h.C = s->C;
+    a.h.D = s->D;
+    a.h.eps = s->eps;
+    a.h.L = s->L;
+    a.h.seed = s->seed;
+    a.h.step0 = s->step + pos;
+    a.h.chain_offset = s->chain_offset;
+    a.h.n_steps = (int)n;
+    a.h.collect_from = (int)cf;
+    a.h.sample_row0 = row0;
+    a.h.lf_unroll = lf_unroll;
+    a.eps = h.eps;
+    a.eps_bar = h.eps_bar;
+    a.h_bar = h.h_bar;
+    a.mu = h.mu;
+    a.dinv = h.dinv;
+    a.dsq = h.dsq;
+    a.rmean = h.rmean;
+    a.rm2 = h.rm2;
+    a.delta = h.delta;
+    a.k0 = h.k;
+    a.rn0 = h.rn;
+    a.m0 = pos;
+    a.sb = h.sb;
+    a.lim = lim;
+    hipError_t e = launch_hmc_adapt(s->dt, s->tg, s->lay, a, in_warm ? h.mode : 0, s->stream, ev);
+    if (e == hipSuccess && in_warm) {
+      h.k += n;
+      if (h.mode == 2) {  // transitions m in (pos, pos + n] with sb < m < lim
+        const long long lo = std::max(pos + 1, h.sb + 1), hi = std::min(pos + n, lim - 1);
+        if (hi >= lo) h.rn += hi - lo + 1;
+      }
+      if (upd && h.rn >= 5) {  // (fewer than 5 positions: nothing changes, the statistics are kept)
+        e = launch_hmc_adapt_window(s->dt, s->C, s->D, h.reg, h.jit, h.rn, h.eps, h.eps_bar, h.h_bar, h.mu,
+                                    h.dinv, h.dsq, h.rmean, h.rm2, s->stream);
+        h.k = 0;
+        h.rn = 0;
+      }
+      if (e == hipSuccess && pos + n == warm) {  // the warm-up is over: eps = eps_bar, frozen from here on
+        e = hipMemcpyAsync(h.eps, h.eps_bar, (size_t)s->C * s->esz, hipMemcpyDeviceToDevice, s->stream);
+        h.armed = false;
+      }
+    }
+    if (e != hipSuccess) {
+      set_error(std::string("kernel launch failed: ") + hipGetErrorString(e));
+      return GM_EHIP;
+    }
+    ++n_launch;
+    if (hook && *hook) {
+      const int rc = (*hook)(pos + n);
+      if (rc) return rc;
+    }
+    pos += n;
+  }
+  s->step += total;
+  s->total_steps += total;
+  if (!(s->async_runs && s->may_async)) GM_HIP(hipStreamSynchronize(s->stream));
+  s->last_ms_pending = true;
+  s->last_launches = n_launch;
+  return GM_OK;
+}
+
 static int run_impl(gm_sampler* s, int64_t n_collect, int64_t n_discard, int progress) {
   GM_REQ(s, "sampler is NULL");
   s->last_rows = n_collect;
@@ -857,6 +1097,7 @@ static int run_impl(gm_sampler* s, int64_t n_collect, int64_t n_discard, int pro
   int rc = ensure_buf(&s->d_samples, &s->samples_bytes, (size_t)n_collect * s->C * s->D * s->esz);
   if (rc) return rc;
   long long total = n_discard + n_collect;
+  s->ha.pending_warm = n_discard;
   if (s->kind == K_NUTS && !progress) {
     // NUTS::run performs n_collect + n_discard - 1 transitions (nuts.rs:232-257);
     // row r is the state after n_discard + r of them.
@@ -1029,6 +1270,7 @@ int gm_run_progress_cb(gm_sampler* s, int64_t n_collect, int64_t n_discard, void
     // burn-in, then the collection with a MultiChainTracker stepped on the
     // current positions at each sync point (hmc.rs:252-290)
     if (n_discard > 0) {
+      s->ha.pending_warm = n_discard;
       rc = run_steps(s, n_discard, n_discard, 1);
       if (rc) return rc;
     }
@@ -1183,6 +1425,148 @@ int gm_get_leapfrog_counts(gm_sampler* s, int64_t* out) {
   return GM_OK;
 }
 
+int gm_hmc_set_adaptation(gm_sampler* s, int32_t mode, double target_accept, int64_t start_buffer,
+                          int64_t end_buffer, int64_t initial_window, double regularize, double jitter) {
+  int rc = hmc_adapt_callable(s);
+  if (rc) return rc;
+  GM_REQ(mode >= 0 && mode <= 2, "mode must be 0 (off), 1 (step size) or 2 (step size + diagonal metric)");
+  GM_REQ(target_accept > 0 && target_accept < 1, "target_accept must be in (0, 1)");
+  GM_REQ(start_buffer >= 0 && end_buffer >= 0 && initial_window >= 0, "window sizes must be >= 0");
+  GM_REQ(regularize >= 0 && regularize <= 1, "regularize must be in [0, 1]");
+  GM_REQ(!std::isnan(jitter), "jitter is NaN");
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  if (mode == 0) {  // back to the scalar step size, the identity metric and hmc_kernel
+    hmc_adapt_free(s);
+    return GM_OK;
+  }
+  const size_t C = (size_t)s->C;
+  std::vector<double> e(C, hmc_eps_rounded(s)), mu(C);
+  if (s->ha.has) {
+    rc = get_as(s->dt, s->ha.eps, C, e.data());
+    if (rc) return rc;
+  }
+  for (size_t c = 0; c < C; ++c) {
+    GM_REQ(e[c] > 0 && std::isfinite(e[c]), "step sizes must be finite and > 0 to be adapted");
+    mu[c] = std::log(10.0 * e[c]);
+  }
+  if (s->tg.kind == GM_TARGET_CUSTOM) {
+    rc = jit_prepare(mode == 1 ? JIT_HMC_ADAPT1 : JIT_HMC_ADAPT2, s->dt, s->tg);
+    if (rc) return rc;
+  }
+  rc = hmc_adapt_ensure(s);
+  if (rc) return rc;
+  HmcAdapt& h = s->ha;
+  // start state: eps_bar = eps, mu = ln(10 eps), h_bar = 0, k = 0, no statistics
+  GM_HIP(hipMemcpy(h.eps_bar, h.eps, C * s->esz, hipMemcpyDeviceToDevice));
+  rc = put_as(s->dt, mu.data(), C, h.mu);
+  if (rc) return rc;
+  GM_HIP(hipMemset(h.h_bar, 0, C * s->esz));
+  GM_HIP(hipMemset(h.rmean, 0, C * s->D * s->esz));
+  GM_HIP(hipMemset(h.rm2, 0, C * s->D * s->esz));
+  h.mode = mode;
+  h.armed = true;
+  h.delta = target_accept;
+  h.sb = start_buffer;
+  h.eb = end_buffer;
+  h.iw = initial_window;
+  h.reg = regularize;
+  h.jit = jitter;
+  h.k = 0;
+  h.rn = 0;
+  return GM_OK;
+}
+
+int gm_hmc_set_step_sizes(gm_sampler* s, const double* eps) {
+  int rc = hmc_adapt_callable(s);
+  if (rc) return rc;
+  GM_REQ(eps, "eps is NULL");
+  const size_t C = (size_t)s->C;
+  for (size_t c = 0; c < C; ++c) {
+    const double v = s->dt == GM_F32 ? (double)(float)eps[c] : eps[c];
+    GM_REQ(v > 0 && std::isfinite(v), "step sizes must be finite and > 0");
+  }
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  rc = hmc_adapt_ensure(s);
+  if (rc) return rc;
+  rc = put_as(s->dt, eps, C, s->ha.eps);
+  if (!rc) rc = put_as(s->dt, eps, C, s->ha.eps_bar);
+  if (rc) return rc;
+  if (s->ha.armed) {  // an armed warm-up starts from these: mu = ln(10 eps)
+    std::vector<double> mu(C);
+    for (size_t c = 0; c < C; ++c) mu[c] = std::log(10.0 * (s->dt == GM_F32 ? (double)(float)eps[c] : eps[c]));
+    rc = put_as(s->dt, mu.data(), C, s->ha.mu);
+  }
+  return rc;
+}
+
+int gm_hmc_get_step_sizes(gm_sampler* s, double* eps, double* eps_bar) {
+  int rc = hmc_adapt_callable(s);
+  if (rc) return rc;
+  const size_t C = (size_t)s->C;
+  if (!s->ha.has) {
+    for (size_t c = 0; c < C; ++c) {
+      if (eps) eps[c] = hmc_eps_rounded(s);
+      if (eps_bar) eps_bar[c] = hmc_eps_rounded(s);
+    }
+    return GM_OK;
+  }
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  if (eps) rc = get_as(s->dt, s->ha.eps, C, eps);
+  if (!rc && eps_bar) rc = get_as(s->dt, s->ha.eps_bar, C, eps_bar);
+  return rc;
+}
+
+int gm_hmc_set_metric(gm_sampler* s, const void* diag_inv) {
+  int rc = hmc_adapt_callable(s);
+  if (rc) return rc;
+  GM_REQ(diag_inv, "diag_inv is NULL");
+  const size_t n = (size_t)s->C * s->D;
+  // checked in full before anything changes; sqrt(M) = 1/sqrt(M^-1) in the sampler dtype
+  std::vector<unsigned char> sq(n * s->esz);
+  for (size_t i = 0; i < n; ++i) {
+    if (s->dt == GM_F32) {
+      const float v = ((const float*)diag_inv)[i];
+      GM_REQ(v > 0 && std::isfinite(v), "diag_inv entries must be finite and > 0");
+      ((float*)sq.data())[i] = 1.0f / gsqrt(v);
+    } else {
+      const double v = ((const double*)diag_inv)[i];
+      GM_REQ(v > 0 && std::isfinite(v), "diag_inv entries must be finite and > 0");
+      ((double*)sq.data())[i] = 1.0 / gsqrt(v);
+    }
+  }
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  rc = hmc_adapt_ensure(s);
+  if (rc) return rc;
+  GM_HIP(hipMemcpy(s->ha.dinv, diag_inv, n * s->esz, hipMemcpyHostToDevice));
+  GM_HIP(hipMemcpy(s->ha.dsq, sq.data(), n * s->esz, hipMemcpyHostToDevice));
+  return GM_OK;
+}
+
+int gm_hmc_get_metric(gm_sampler* s, void* diag_inv, void* diag_sqrt) {
+  int rc = hmc_adapt_callable(s);
+  if (rc) return rc;
+  const size_t n = (size_t)s->C * s->D;
+  if (!s->ha.has) {
+    for (void* o : {diag_inv, diag_sqrt}) {
+      if (!o) continue;
+      for (size_t i = 0; i < n; ++i) {
+        if (s->dt == GM_F32) ((float*)o)[i] = 1.0f;
+        else ((double*)o)[i] = 1.0;
+      }
+    }
+    return GM_OK;
+  }
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  if (diag_inv) GM_HIP(hipMemcpy(diag_inv, s->ha.dinv, n * s->esz, hipMemcpyDeviceToHost));
+  if (diag_sqrt) GM_HIP(hipMemcpy(diag_sqrt, s->ha.dsq, n * s->esz, hipMemcpyDeviceToHost));
+  return GM_OK;
+}
+
 int gm_nuts_get_step_size(gm_sampler* s, double* eps, double* eps_bar) {
   GM_REQ(s, "sampler is NULL");
   GM_REQ(s->kind == K_NUTS, "not a NUTS sampler");
@@ -1293,6 +1677,12 @@ struct StateHeader {
   uint64_t seed, step;
   int64_t total_steps;
   uint32_t chain_offset;
+  // NUTS: the metric mode. HMC: 1 when the blob carries per-chain step sizes
+  // and a metric (HmcAdapt), whose configuration and counters then use the
+  // NUTS warm-up fields: m_sb, m_eb, sched_len = initial_window, m_reg,
+  // m_jit, target_accept, nuts_m = mode | armed << 8, nuts_n_discard = k,
+  // sched_next = rn. A sampler without that state writes 0 here and zeros
+  // there, as it always did.
   int32_t mass_mode;
   int64_t m_sb, m_eb, sched_next, sched_len;
   double m_reg, m_jit;
@@ -1329,6 +1719,11 @@ std::vector<StatePart> state_parts_for(gm_sampler* s, int mass_mode) {
       v.push_back({n.mchol, C * D * D * e});
     }
   }
+  if (s->kind == K_HMC && mass_mode) {
+    HmcAdapt& h = s->ha;
+    for (void* p : {h.eps, h.eps_bar, h.h_bar, h.mu}) v.push_back({p, C * e});
+    for (void* p : {h.dinv, h.dsq, h.rmean, h.rm2}) v.push_back({p, C * D * e});
+  }
   return v;
 }
 size_t parts_bytes(const std::vector<StatePart>& v) {
@@ -1336,7 +1731,10 @@ size_t parts_bytes(const std::vector<StatePart>& v) {
   for (auto& p : v) b += p.bytes;
   return b;
 }
-size_t state_bytes(gm_sampler* s) { return parts_bytes(state_parts_for(s, s->kind == K_NUTS ? s->nuts.mass_mode : 0)); }
+int state_mode(gm_sampler* s) {
+  return s->kind == K_NUTS ? s->nuts.mass_mode : s->kind == K_HMC && s->ha.has ? 1 : 0;
+}
+size_t state_bytes(gm_sampler* s) { return parts_bytes(state_parts_for(s, state_mode(s))); }
 }  // namespace
 
 extern "C" {
@@ -1417,6 +1815,19 @@ int gm_state_save(gm_sampler* s, void* out, uint64_t bytes) {
     h.nuts_m = n.m;
     h.nuts_n_discard = n.n_discard;
   }
+  if (s->kind == K_HMC && s->ha.has) {
+    const HmcAdapt& a = s->ha;
+    h.mass_mode = 1;
+    h.m_sb = a.sb;
+    h.m_eb = a.eb;
+    h.sched_len = a.iw;
+    h.m_reg = a.reg;
+    h.m_jit = a.jit;
+    h.target_accept = a.delta;
+    h.nuts_m = a.mode | (a.armed ? 1 << 8 : 0);
+    h.nuts_n_discard = a.k;
+    h.sched_next = a.rn;
+  }
   unsigned char* o = (unsigned char*)out;
   memcpy(o, &h, sizeof(h));
   o += sizeof(h);
@@ -1441,6 +1852,14 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
   switch (s->kind) {
     case K_HMC:
       GM_REQ(h.eps == s->eps && h.L == s->L, "state blob is for a different step size / n_leapfrog");
+      GM_REQ(h.mass_mode == 0 || h.mass_mode == 1, "corrupt state blob (per-chain state flag)");
+      if (h.mass_mode) {
+        GM_REQ((h.nuts_m & 0xff) <= 2 && (h.nuts_m & ~0x1ffLL) == 0 && h.nuts_n_discard >= 0 &&
+                   h.sched_next >= 0 && h.m_sb >= 0 && h.m_eb >= 0 && h.sched_len >= 0,
+               "corrupt state blob (warm-up configuration)");
+        GM_REQ(s->D <= 1024 && !layout_is_wide(s->lay),
+               "state blob carries per-chain step sizes / metric: not for a wide layout");
+      }
       break;
     case K_MH:
       GM_REQ(h.prop_std == s->prop_std, "state blob is for a different proposal std");
@@ -1452,7 +1871,7 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
       GM_REQ(h.nuts_m >= 0 && h.nuts_n_discard >= 0 && h.sched_len >= 0, "corrupt state blob (counters)");
       break;
   }
-  if (s->kind != K_NUTS) GM_REQ(h.mass_mode == 0, "corrupt state blob (mass mode)");
+  if (s->kind == K_MH) GM_REQ(h.mass_mode == 0, "corrupt state blob (mass mode)");
   GM_REQ(bytes >= parts_bytes(state_parts_for(s, h.mass_mode)), "state blob too short");
   GM_HIP(hipSetDevice(s->device));
   GM_HIP(hipStreamSynchronize(s->stream));
@@ -1460,6 +1879,14 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
     const int rc = nuts_set_mass(&s->nuts, s->dt, s->C, s->D, h.mass_mode, h.m_sb, h.m_eb, 0,
                                  h.m_reg, h.m_jit);
     if (rc) return rc;
+  }
+  if (s->kind == K_HMC) {
+    if (h.mass_mode) {
+      const int rc = hmc_adapt_ensure(s);
+      if (rc) return rc;
+    } else {
+      hmc_adapt_free(s);  // the blob's sampler ran the plain path
+    }
   }
   const unsigned char* p = (const unsigned char*)in + sizeof(h);
   for (auto& part : state_parts_for(s, h.mass_mode)) {
@@ -1474,6 +1901,19 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
     s->nuts.sched_len = h.sched_len;
     s->nuts.m = h.nuts_m;
     s->nuts.n_discard = h.nuts_n_discard;
+  }
+  if (s->kind == K_HMC && h.mass_mode) {
+    HmcAdapt& a = s->ha;
+    a.sb = h.m_sb;
+    a.eb = h.m_eb;
+    a.iw = h.sched_len;
+    a.reg = h.m_reg;
+    a.jit = h.m_jit;
+    a.delta = h.target_accept;
+    a.mode = (int)(h.nuts_m & 0xff);
+    a.armed = (h.nuts_m >> 8) & 1;
+    a.k = h.nuts_n_discard;
+    a.rn = h.sched_next;
   }
   return GM_OK;
 }
@@ -1563,6 +2003,7 @@ int gm_destroy(gm_sampler* s) {
   if (s->d_trk) hipFree(s->d_trk);
   if (s->d_mct) hipFree(s->d_mct);
   nuts_free_state(&s->nuts);
+  hmc_adapt_free(s);
   if (s->stream) hipStreamDestroy(s->stream);
   delete s;
   return GM_OK;

@@ -1,0 +1,5 @@
+// hmc_adapt_f64_m0.hip — hmc_adapt_kernel<double, ..., MODE 0> for every layout and built-in target (hmc_adapt_part.inc).
+#define GM_HA_T double
+#define GM_HA_MODE 0
+#define GM_HA_NAME launch_hmc_adapt_f64_m0
+#include "hmc_adapt_part.inc"

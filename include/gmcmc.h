@@ -85,7 +85,8 @@ typedef struct gm_target {
 } gm_target;
 
 /* Compile a CUSTOM target's source for the sampler kernels without running it
- * (kind: 1 HMC, 2 MH, 3 NUTS, 0 log-density/gradient); GM_EINVAL with the
+ * (kind: 1 HMC, 2 MH, 3 NUTS, 4 HMC with per-chain step sizes / metric /
+ * warm-up, 0 log-density/gradient); GM_EINVAL with the
  * compiler log in gm_last_error() when it does not compile. */
 int gm_custom_target_check(const char* source, gm_dtype dtype, int64_t dim, int32_t kind);
 
@@ -134,6 +135,50 @@ typedef struct gm_sampler gm_sampler;
 int gm_hmc_create(const gm_target* target, gm_dtype dtype, int64_t n_chains, int64_t dim,
                   const void* init, double step_size, int64_t n_leapfrog,
                   int64_t chain_offset, gm_sampler** out);
+
+/* ---- HMC warm-up: per-chain step sizes and a per-chain diagonal metric ----
+ * No reference counterpart (the reference's HMC takes one step size and the
+ * identity metric, hmc.rs:113-134). A sampler on which none of these calls
+ * was made runs exactly as before. They need an HMC sampler (GM_ESTATE
+ * otherwise) with dim <= 1024 (GM_EINVAL on a wide layout).
+ *
+ * With a metric M (diagonal, per chain) a transition draws p = sqrt(M) z from
+ * the same momentum normals z, drifts with q += eps * M^-1 p and weighs the
+ * kinetic energy 0.5 p' M^-1 p; with equal step sizes and M = I it returns
+ * the bits of the plain path.
+ *
+ * gm_hmc_set_adaptation arms a warm-up: the n_discard transitions of the next
+ * gm_run* call (a run with n_discard == 0 adapts nothing and stays armed)
+ * adapt, per chain, the step size by dual averaging towards target_accept
+ * (gamma .05, t0 10, kappa .75, as NUTS here) and, in mode 2, a diagonal
+ * metric from the Welford variance of the positions in the windows of the
+ * NUTS schedule (start_buffer, end_buffer, initial_window doubling up to 400;
+ * at a window end with >= 5 positions: M^-1 = max((1 - regularize) var +
+ * regularize, max(jitter, 1e-10)), statistics reset, dual averaging restarted
+ * from eps_bar). After the last warm-up transition eps = eps_bar; later runs
+ * and gm_step sample with the frozen step sizes and metric. Calling it again
+ * re-arms. mode 0 drops all per-chain state: the sampler is back on the
+ * creation step size, the identity metric and the plain path.
+ * Metric convention: M^-1 is the regularised sample variance (Stan, PyMC);
+ * the NUTS path follows the reference and stores 1/var in its `inv`.
+ * GM_EINVAL unless 0 < target_accept < 1, the window sizes are >= 0 and
+ * regularize is in [0, 1]. */
+int gm_hmc_set_adaptation(gm_sampler* s, int32_t mode /* 0 off, 1 step size, 2 step size + diagonal metric */,
+                          double target_accept, int64_t start_buffer, int64_t end_buffer,
+                          int64_t initial_window, double regularize, double jitter);
+/* Per-chain step sizes eps[n_chains] (finite, > 0; rounded to the sampler
+ * dtype); eps_bar is set to the same values. */
+int gm_hmc_set_step_sizes(gm_sampler* s, const double* eps);
+/* Per-chain (eps, eps_bar), [n_chains] each, either may be NULL; the creation
+ * step_size for every chain before any of these calls. */
+int gm_hmc_get_step_sizes(gm_sampler* s, double* eps, double* eps_bar);
+/* The metric as M^-1: diag_inv [n_chains][dim] of the sampler dtype, every
+ * entry finite and > 0 (GM_EINVAL otherwise, the sampler unchanged);
+ * sqrt(M) = 1/sqrt(diag_inv) is derived from it. */
+int gm_hmc_set_metric(gm_sampler* s, const void* diag_inv);
+/* M^-1 and sqrt(M), [n_chains][dim] of the sampler dtype, either may be NULL;
+ * ones before any of these calls. */
+int gm_hmc_get_metric(gm_sampler* s, void* diag_inv, void* diag_sqrt);
 
 /* MetropolisHastings::new (metropolis_hastings.rs:151-161) with an
  * IsotropicGaussian proposal of standard deviation proposal_std

@@ -120,10 +120,55 @@ static void argument_checks() {
     }
 }
 
+// The HMC warm-up entry points (gm_hmc_set_adaptation, ...): the sampler kind
+// and every argument are checked before the device is touched, and a state
+// blob that claims per-chain HMC state is sized before it is read.
+static void hmc_adapt_checks() {
+  std::vector<double> eps(7, 0.1), out(7);
+  std::vector<float> m(7 * 5, 1.0f), o(7 * 5);
+  for (int kind : {2, 3}) {  // MH, NUTS: not valid in this sampler's state
+    gm_sampler* s = gm_test_sampler(kind, 0, 7, 5, 0);
+    EXPECT(gm_hmc_set_adaptation(s, 1, 0.8, 75, 50, 25, 0.05, 1e-6) == GM_ESTATE, "adaptation on non-HMC");
+    EXPECT(gm_hmc_set_step_sizes(s, eps.data()) == GM_ESTATE, "step sizes on non-HMC");
+    EXPECT(gm_hmc_get_step_sizes(s, out.data(), nullptr) == GM_ESTATE, "get step sizes on non-HMC");
+    EXPECT(gm_hmc_set_metric(s, m.data()) == GM_ESTATE, "metric on non-HMC");
+    EXPECT(gm_hmc_get_metric(s, o.data(), nullptr) == GM_ESTATE, "get metric on non-HMC");
+    gm_test_sampler_free(s);
+  }
+  gm_sampler* s = gm_test_sampler(1, 0, 7, 5, 0);
+  EXPECT(gm_hmc_set_adaptation(nullptr, 1, 0.8, 75, 50, 25, 0.05, 1e-6) == GM_EINVAL, "null sampler");
+  for (double bad : {0.0, 1.0, 0.0 / 0.0, -1.0, 2.0})
+    EXPECT(gm_hmc_set_adaptation(s, 1, bad, 75, 50, 25, 0.05, 1e-6) == GM_EINVAL, "target_accept");
+  EXPECT(gm_hmc_set_adaptation(s, 5, 0.8, 75, 50, 25, 0.05, 1e-6) == GM_EINVAL, "mode");
+  EXPECT(gm_hmc_set_adaptation(s, 2, 0.8, -1, 50, 25, 0.05, 1e-6) == GM_EINVAL, "start_buffer");
+  EXPECT(gm_hmc_set_adaptation(s, 2, 0.8, 75, 50, 25, -0.1, 1e-6) == GM_EINVAL, "regularize");
+  EXPECT(gm_hmc_set_step_sizes(s, nullptr) == GM_EINVAL, "null eps");
+  eps[6] = -0.1;
+  EXPECT(gm_hmc_set_step_sizes(s, eps.data()) == GM_EINVAL, "negative eps");
+  EXPECT(gm_hmc_set_metric(s, nullptr) == GM_EINVAL, "null metric");
+  for (float bad : {0.0f, -1.0f, 0.0f / 0.0f, 1.0f / 0.0f}) {
+    m[7 * 5 - 1] = bad;  // the last entry: the whole array is read, none past it
+    EXPECT(gm_hmc_set_metric(s, m.data()) == GM_EINVAL, "bad metric entry");
+  }
+  // before any of the set calls: the creation step size and ones, no device needed
+  EXPECT(gm_hmc_get_step_sizes(s, out.data(), nullptr) == GM_OK && out[6] == (double)0.01f, "default step sizes");
+  EXPECT(gm_hmc_get_metric(s, o.data(), nullptr) == GM_OK && o[7 * 5 - 1] == 1.0f, "default metric");
+  // a plain-sized blob whose header claims per-chain state is too short
+  uint64_t need = 0;
+  gm_state_size(s, &need);
+  std::vector<unsigned char> blob(need, 0);
+  gm_test_state_header(s, blob.data());
+  const int32_t one = 1;
+  std::memcpy(blob.data() + 8 + 4 + 4 + 8 + 8 + 8 + 8 + 8 + 4, &one, 4);  // StateHeader::mass_mode
+  EXPECT(gm_state_load(s, blob.data(), need) == GM_EINVAL, "per-chain state flag on a plain-sized blob");
+  gm_test_sampler_free(s);
+}
+
 int main() {
   state_blobs();
   gauss_from_cov();
   argument_checks();
+  hmc_adapt_checks();
   std::printf("%s\n", fails ? "ASAN HOST CHECKS FAILED" : "asan host checks ok");
   return fails ? 1 : 0;
 }
