@@ -49,6 +49,10 @@ class gm_progress(C.Structure):
                 ("max_rhat", C.c_float)]
 
 
+class gm_summary_out(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("mean", "sd", "quantiles", "rhat", "ess_bulk", "ess_tail")]
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(gm_progress))
 
 _vp = C.c_void_p
@@ -112,6 +116,11 @@ SIGNATURES = {
     "gm_destroy": (_ip, [_vp]),
     "gm_split_rhat_ess": (_ip, [_vp, _ip, _i64, _i64, _i64, _vp, _vp]),
     "gm_split_rhat_ess_device": (_ip, [_vp, _ip, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "gm_summary": (_ip, [_vp, _ip, _i64, _i64, _i64, _i32, _vp, C.POINTER(gm_summary_out)]),
+    "gm_summary_device": (_ip, [_vp, _ip, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp,
+                                C.POINTER(gm_summary_out)]),
+    "gm_rank_normalize": (_ip, [_vp, _ip, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "gm_summary_sort_plan": (_ip, [C.POINTER(_i32), _i32]),
     "gm_comm_get_unique_id": (_ip, [_vp]),
     "gm_comm_init": (_ip, [_vp, _i32, _i32, C.POINTER(_vp)]),
     "gm_comm_destroy": (_ip, [_vp]),

@@ -7,7 +7,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .stats import ChainStats, Progress, RunStats, _print_progress, split_rhat_mean_ess_device
+from .stats import (ChainStats, Progress, RunStats, _print_progress, split_rhat_mean_ess_device,
+                    summary_device)
 
 
 @dataclass
@@ -48,6 +49,13 @@ class DeviceSamples:
         self.owner.synchronize()  # an asynchronous run may still be writing them
         return split_rhat_mean_ess_device(self.ptr, self.dtype, self.n_chains, self.n_collect,
                                           self.dim, (self.dim, self.n_chains * self.dim, 1))
+
+    def summary(self, probs=(0.05, 0.5, 0.95)):
+        """stats.summary of these samples, computed where they lie."""
+        self._check_live()
+        self.owner.synchronize()
+        return summary_device(self.ptr, self.dtype, self.n_chains, self.n_collect, self.dim,
+                              (self.dim, self.n_chains * self.dim, 1), probs)
 
 
 class Sampler:

@@ -49,6 +49,101 @@ def split_rhat_mean_ess_device(dev_ptr: int, dtype, n_chains: int, n_draws: int,
 
 
 @dataclass
+class Summary:
+    """Per-parameter posterior summary (stats.summary, DeviceSamples.summary);
+    every array is f64 of length n_params, quantiles [len(probs), n_params]."""
+    mean: np.ndarray
+    sd: np.ndarray
+    quantiles: np.ndarray
+    rhat: np.ndarray
+    ess_bulk: np.ndarray
+    ess_tail: np.ndarray
+    probs: tuple
+
+    def __str__(self) -> str:
+        qh = "".join(f" {f'q{100 * p:g}':>10}" for p in self.probs)
+        rows = [f"{'param':>6} {'mean':>10} {'sd':>10}{qh} {'rhat':>7} {'ess_bulk':>9} {'ess_tail':>9}"]
+        for p in range(len(self.mean)):
+            q = "".join(f" {v:10.4g}" for v in self.quantiles[:, p])
+            rows.append(f"{p:>6} {self.mean[p]:10.4g} {self.sd[p]:10.4g}{q} {self.rhat[p]:7.4f} "
+                        f"{self.ess_bulk[p]:9.1f} {self.ess_tail[p]:9.1f}")
+        return "\n".join(rows)
+
+
+def _summary_call(call, n_params: int, probs) -> Summary:
+    probs = tuple(float(p) for p in probs)
+    pr = np.asarray(probs, dtype=np.float64)
+    f = {n: np.empty(n_params) for n in ("mean", "sd", "rhat", "ess_bulk", "ess_tail")}
+    f["quantiles"] = np.empty((len(probs), n_params))
+    out = _lib.gm_summary_out(**{n: a.ctypes.data for n, a in f.items()})
+    _lib.check(call(len(probs), _lib.ptr(pr), C.byref(out)))
+    return Summary(probs=probs, **f)
+
+
+def _sample_array(sample) -> np.ndarray:
+    x = np.asarray(sample)
+    if x.dtype not in (np.float32, np.float64):
+        x = x.astype(np.float64)
+    x = np.ascontiguousarray(x)
+    if x.ndim != 3:
+        raise ValueError("sample must be [chains, draws, params]")
+    return x
+
+
+def summary(sample, probs=(0.05, 0.5, 0.95)) -> Summary:
+    """Posterior summary of a host [chains, draws, params] sample (draws >= 4),
+    computed on the GPU in the sample's own dtype (f32 or f64): mean, sd
+    (ddof = 1) and quantiles (numpy's linear interpolation) of the draws, and
+    the rank-normalised diagnostics of Vehtari et al. 2021: rhat = the larger of
+    the bulk and the folded split-R-hat, ess_bulk, ess_tail (5 % / 95 %).
+
+    Differences from Stan / ArviZ: the ESS is this project's Appendix-B
+    estimator (Geyer's initial monotone sequence as in split_rhat_mean_ess)
+    without the M log10(M) cap, and the tail indicators use the order
+    statistic floor((M - 1) q) rather than an interpolated quantile. rhat has
+    the usual orientation sqrt(V/W) >= 1; split_rhat_mean_ess keeps the
+    reference's sqrt(W/V). A parameter with a non-finite draw is NaN
+    throughout; a constant one has NaN rhat / ESS."""
+    x = _sample_array(sample)
+    c, n, p = x.shape
+    lib = _lib.require_gpu()
+    return _summary_call(lambda k, pr, out: lib.gm_summary(_lib.ptr(x), _lib.dtype_code(x.dtype), c, n, p, k, pr,
+                                                           out), p, probs)
+
+
+def summary_device(dev_ptr: int, dtype, n_chains: int, n_draws: int, n_params: int,
+                   strides: tuple[int, int, int], probs=(0.05, 0.5, 0.95)) -> Summary:
+    """Same, on device memory (element strides: chain, draw, param)."""
+    lib = _lib.require_gpu()
+    return _summary_call(lambda k, pr, out: lib.gm_summary_device(
+        C.c_void_p(dev_ptr), _lib.dtype_code(dtype), n_chains, n_draws, n_params, strides[0], strides[1],
+        strides[2], k, pr, out), n_params, probs)
+
+
+def rank_normalize(sample, folded: bool = False) -> tuple[np.ndarray, np.ndarray]:
+    """(ranks, z) of a host [chains, draws, params] sample, both f64 of the
+    sample's shape: the 1-based tie-averaged ranks of the pooled split draws
+    (first and last draws // 2 of every chain; an odd count's middle draw is
+    NaN) and their normal scores Phi^-1((r - 3/8) / (M + 1/4)); folded: those
+    of |x - pooled median|."""
+    x = _sample_array(sample)
+    c, n, p = x.shape
+    r = np.empty(x.shape)
+    z = np.empty(x.shape)
+    lib = _lib.require_gpu()
+    _lib.check(lib.gm_rank_normalize(_lib.ptr(x), _lib.dtype_code(x.dtype), c, n, p, int(bool(folded)),
+                                     _lib.ptr(r), _lib.ptr(z)))
+    return r, z
+
+
+def sort_plan() -> dict:
+    """The summary sort's internal sizes (gm_summary_sort_plan)."""
+    v = (C.c_int32 * 4)()
+    _lib.check(_lib.load().gm_summary_sort_plan(v, 4))
+    return {"lds_max": v[0], "tile": v[1], "radix_bits": v[2], "chunk_params": v[3]}
+
+
+@dataclass
 class BasicStats:
     name: str
     min: float

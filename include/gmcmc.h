@@ -383,6 +383,59 @@ int gm_split_rhat_ess_device(const void* dev_sample, gm_dtype dtype, int64_t n_c
                              int64_t stride_draw, int64_t stride_param, float* rhat_out,
                              float* ess_out);
 
+/* ---- posterior summary (not in the reference) ----------------------------
+ * Location, scale, quantiles and the rank-normalised diagnostics of Vehtari
+ * et al. 2021 per parameter, computed on the device from a [C][N][P] sample
+ * (N >= 4). With h = N / 2, Y the 2C split chains (first and last h draws of
+ * each chain; an odd N's middle draw is in none) and M = 2 C h pooled values:
+ *   ranks      1-based average ranks of Y among the M pooled values, in the
+ *              sample's own dtype (-0 == +0; an f64 sample is never rounded)
+ *   z          Phi^-1((r - 3/8) / (M + 1/4))
+ *   ess_bulk   ESS of the Appendix-B estimator (the one behind
+ *              gm_split_rhat_ess) applied to z
+ *   rhat       max over z and z_fold of sqrt(V/W): the usual orientation,
+ *              >= 1 when chains disagree (gm_split_rhat_* report sqrt(W/V) and
+ *              keep doing so). z_fold are the normal scores of |Y - median|,
+ *              formed and ranked in f64
+ *   ess_tail   min of the ESS of I(Y <= y_(k05)) and of I(Y <= y_(k95)), y_(k)
+ *              the 0-based k-th pooled order statistic, k_q = floor((M-1) q)
+ *   quantiles  of Y, linear interpolation between order statistics
+ *              (numpy.quantile's default), in f64
+ *   mean, sd   over all C N draws, sd with ddof = 1, in f64
+ * Unlike Stan the ESS has no M log10(M) cap. A parameter whose pooled values
+ * hold a NaN or an infinity reports NaN in every field; one whose pooled
+ * values are all equal reports NaN for rhat, ess_bulk and ess_tail and its
+ * exact mean and quantiles.
+ * Every entry point returns GM_EINVAL before any device call for a bad dtype,
+ * a NULL sample or out, n_chains < 1, n_draws < 4, n_params < 1, n_probs
+ * outside [0, 32], a prob outside [0, 1] (or NaN), or M >= 2^31.
+ * Host variant: sample is host [n_chains][n_draws][n_params]. Device variant:
+ * a device pointer with element strides (chain, draw, param). */
+typedef struct gm_summary_out { /* host arrays, any may be NULL */
+  double* mean;      /* [P] */
+  double* sd;        /* [P] */
+  double* quantiles; /* [n_probs][P] */
+  double* rhat;      /* [P] rank-normalised, max(bulk, folded), sqrt(V/W) */
+  double* ess_bulk;  /* [P] */
+  double* ess_tail;  /* [P] */
+} gm_summary_out;
+int gm_summary(const void* sample, gm_dtype dtype, int64_t n_chains, int64_t n_draws,
+               int64_t n_params, int32_t n_probs, const double* probs, gm_summary_out* out);
+int gm_summary_device(const void* dev_sample, gm_dtype dtype, int64_t n_chains, int64_t n_draws,
+                      int64_t n_params, int64_t stride_chain, int64_t stride_draw,
+                      int64_t stride_param, int32_t n_probs, const double* probs,
+                      gm_summary_out* out);
+/* Ranks (exact, multiples of 1/2) and normal scores of the pooled split draws
+ * of a host sample, as host [C][N][P] f64 with NaN in an odd N's middle draw;
+ * folded != 0: those of |x - median|. Either output may be NULL. */
+int gm_rank_normalize(const void* sample, gm_dtype dtype, int64_t n_chains, int64_t n_draws,
+                      int64_t n_params, int32_t folded, double* ranks_out, double* z_out);
+/* The sort's internal sizes, for tests: [0] the largest M of the
+ * one-workgroup (LDS) path, [1] elements per block of the global radix path,
+ * [2] radix bits per pass, [3] parameters per chunk at most. Writes
+ * min(cap, 4) values. */
+int gm_summary_sort_plan(int32_t* out, int32_t cap);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------
  * Chains are sharded in contiguous blocks; sampling needs no communication.
  * The only exchange is an RCCL all-gather of per-split-chain summaries for
