@@ -126,6 +126,56 @@ __device__ __forceinline__ int xor16_sum(int v) {
   return (int)r[0] + (int)r[1];
 }
 
+// The two cross-row stages of N 64-lane sums whose lanes hold their row
+// totals r_r: rows 1 and 3 add the broadcast of rows 0 and 2 (r1+r0, r3+r2),
+// then row 3 adds row 1's value, so every lane of row 3 (48..63) ends with
+// (r3+r2) + (r1+r0), bitwise the l^16, l^32 stage result (r0+r1)+(r2+r3)
+// since IEEE addition commutes. Rows 0..2 are left with partial sums that no
+// caller reads.
+// Precondition: all 64 lanes are active. A 64-lane group is a whole wave and
+// every caller reaches its sums wave-converged (one chain per wave, or the
+// block-uniform control flow of the wide layouts). A row broadcast from a
+// disabled lane writes nothing: the move form would add 0 there, the f32 add
+// form would leave the row's partial sum, and neither is the chain's total.
+//
+// The move form, for every type (there is no 64-bit DPP add) and stage-major:
+// a masked DPP move (0 in the rows outside the mask) and an add.
+template <int N, class T> __device__ __forceinline__ void cross_rows_moves(T (&v)[N]) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = v[k] + dpp_rows<DPP_ROW_BCAST15, 0xa>(v[k]);
+  if constexpr (N > 1) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = v[k] + dpp_rows<DPP_ROW_BCAST31, 0x8>(v[k]);
+}
+// f32: one DPP-fed add per stage and sum. (Written as a masked DPP move and an
+// add, the compiler has to keep the move, a zero for the rows outside the
+// mask and a wait state: x + 0 is not x for -0.) The hazard recogniser does
+// not look inside an asm statement, so each statement carries the two wait
+// states a DPP read needs after a VALU write of its source; from three sums
+// up the other sums' adds are those wait states between the stages.
+#define GM_ADD15(X) "v_add_f32_dpp " X ", " X ", " X " row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+#define GM_ADD31(X) "v_add_f32_dpp " X ", " X ", " X " row_bcast:31 row_mask:0x8 bank_mask:0xf\n\t"
+template <int N> __device__ __forceinline__ void cross_rows(float (&v)[N]) {
+  if constexpr (N == 1) {
+    asm volatile("s_nop 1\n\t" GM_ADD15("%0") "s_nop 1\n\t" GM_ADD31("%0") : "+v"(v[0]));
+  } else if constexpr (N == 2) {
+    asm volatile("s_nop 1\n\t" GM_ADD15("%0") GM_ADD15("%1") "s_nop 0\n\t" GM_ADD31("%0") GM_ADD31("%1")
+                 : "+v"(v[0]), "+v"(v[1]));
+  } else if constexpr (N == 3) {
+    asm volatile("s_nop 1\n\t" GM_ADD15("%0") GM_ADD15("%1") GM_ADD15("%2") GM_ADD31("%0") GM_ADD31("%1") GM_ADD31("%2")
+                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]));
+  } else if constexpr (N == 4) {
+    asm volatile("s_nop 1\n\t" GM_ADD15("%0") GM_ADD15("%1") GM_ADD15("%2") GM_ADD15("%3")
+                 GM_ADD31("%0") GM_ADD31("%1") GM_ADD31("%2") GM_ADD31("%3")
+                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
+  } else {  // (no caller sums more than four at once)
+    cross_rows_moves(v);
+  }
+}
+#undef GM_ADD15
+#undef GM_ADD31
+template <int N, class T> __device__ __forceinline__ void cross_rows(T (&v)[N]) { cross_rows_moves(v); }
+
 template <int LPC, class T> __device__ __forceinline__ T group_sum(T v) {
   if constexpr (LPC > 64) {
     T t[1] = {group_sum<64>(v)};
@@ -138,14 +188,12 @@ template <int LPC, class T> __device__ __forceinline__ T group_sum(T v) {
   if constexpr (LPC >= 16) v = v + dpp<DPP_ROW_MIRROR>(v);
   if constexpr (LPC == 32) v = xor16_sum(v);
   if constexpr (LPC >= 64) {
-    // Every lane of row r now holds the row total r_r. Rows 1 and 3 add the
-    // broadcast of rows 0 and 2 (r1+r0, r3+r2), then row 3 adds row 1's value:
-    // lane 63 = (r3+r2) + (r1+r0), bitwise the l^16, l^32 stage result
-    // (r0+r1)+(r2+r3) since IEEE addition commutes. The total comes back
-    // wave-uniform (one chain per wave).
-    v = v + dpp_rows<DPP_ROW_BCAST15, 0xa>(v);
-    v = v + dpp_rows<DPP_ROW_BCAST31, 0x8>(v);
-    v = lane63(v);
+    // Every lane of row r now holds the row total r_r; cross_rows leaves the
+    // chain's total in row 3, and it comes back wave-uniform from lane 63
+    // (one chain per wave).
+    T t[1] = {v};
+    cross_rows(t);
+    v = lane63(t[0]);
   }
   return v;
 }
@@ -156,7 +204,13 @@ template <int LPC, class T> __device__ __forceinline__ T group_sum(T v) {
 template <class X> struct Bare { using type = X; };
 template <class X> struct Bare<const X> { using type = X; };
 
-template <int LPC, int N, class T> __device__ __forceinline__ void group_sum_n(T (&v)[N]) {
+// UNIFORM = false (64-lane groups only): without the last step, the read of
+// lane 63 into a wave-uniform value. The totals stay where the stages leave
+// them, in every lane of row 3 (lanes 48..63); the other lanes hold partial
+// sums. For callers that go on computing in the vector registers and take
+// their wave-uniform decision from a row-3 bit of a compare.
+template <int LPC, bool UNIFORM, int N, class T> __device__ __forceinline__ void group_sum_n_impl(T (&v)[N]) {
+  static_assert(UNIFORM || LPC == 64, "row-3 totals: one chain per wave");
   // sched_barrier(0) between stages keeps the machine scheduler from
   // regrouping the stages per sum (it does, without them)
 #define GM_STAGE(COND, EXPR)                                  \
@@ -169,12 +223,20 @@ template <int LPC, int N, class T> __device__ __forceinline__ void group_sum_n(T
   GM_STAGE(LPC >= 8, v[k] + dpp<DPP_ROW_HALF_MIRROR>(v[k]))
   GM_STAGE(LPC >= 16, v[k] + dpp<DPP_ROW_MIRROR>(v[k]))
   GM_STAGE(LPC == 32, xor16_sum(v[k]))
-  GM_STAGE(LPC >= 64, v[k] + (dpp_rows<DPP_ROW_BCAST15, 0xa>(v[k])))
-  GM_STAGE(LPC >= 64, v[k] + (dpp_rows<DPP_ROW_BCAST31, 0x8>(v[k])))
-  GM_STAGE(LPC >= 64, lane63(v[k]))
+  if constexpr (LPC >= 64) {
+    __builtin_amdgcn_sched_barrier(0);
+    cross_rows(v);
+  }
+  GM_STAGE(LPC >= 64 && UNIFORM, lane63(v[k]))
 #undef GM_STAGE
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (LPC > 64) block_totals<LPC, N>(v);
+}
+template <int LPC, int N, class T> __device__ __forceinline__ void group_sum_n(T (&v)[N]) {
+  group_sum_n_impl<LPC, true>(v);
+}
+template <int N, class T> __device__ __forceinline__ void group_sum_n_row3(T (&v)[N]) {
+  group_sum_n_impl<64, false>(v);
 }
 // lane l receives lane l+1's value. Wave-wide DPP shift: at a group's last
 // lane the value comes from the next group (or 0); callers mask it, since a

@@ -1,14 +1,38 @@
-// hmc_device.h — the HMC transition kernels (device code only; compiled
-// ahead of time by hmc_kernels.hip and at run time for user targets by
-// gm_jit.cpp). See hmc_kernels.hip for the algorithm notes.
+// hmc_device.h — the HMC transition kernels (device code only). hmc_kernel is
+// compiled ahead of time by hmc_f32.hip and hmc_f64.hip (hmc_part.inc, one
+// translation unit per dtype so that they build in parallel), hmc_wide_kernel
+// by hmc_kernels.hip, and hmc_kernel at run time for user targets by
+// gm_jit.cpp. The algorithm notes are at the top of hmc_kernels.hip, which
+// also holds launch_hmc, the one entry point of all three.
 #pragma once
 #include "gm_device.h"
 #include "gm_launch.h"
 
 namespace gm {
 
-template <class T, int LPC, int E, class TG>
+// a compile-time index handed to a generic lambda, and f(IntC<K>) for K < S
+template <int V> struct IntC { static constexpr int v = V; };
+template <int K, int S, class F> __device__ __forceinline__ void for_each_k(F&& f) {
+  if constexpr (K < S) {
+    f(IntC<K>{});
+    for_each_k<K + 1, S>(f);
+  }
+}
+
+// LF: the leapfrog loop form (1, 2 or 4 leapfrogs per trip) as a constant, or
+// 0 for the launch's a.lf_unroll (all three forms in the code).
+//
+// One chain per wave (LPC = 64): the per-chain sums of a transition are left
+// in row 3 of the wave (lanes 48..63, group_sum_n_row3) and everything derived
+// from them (the kinetic energies, log_alpha, the chain's logp) is computed
+// there in the vector registers, without the read of lane 63 into a scalar
+// and back. The block's S accept log-uniforms sit in lanes 64-S..63 of one
+// register, so the decision of the block's k-th transition is bit 64-S+k of
+// one vector compare, and the branch on it is wave-uniform. The accept count
+// and the sample row pointer are then scalars.
+template <class T, int LPC, int E, class TG, int LF = 0>
 __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
+  constexpr bool W1 = LPC == 64;
   const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long c = gtid / LPC;
   const int lane = (int)(gtid % LPC);
@@ -30,7 +54,7 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
   // (accept uniform) then run on the scalar unit
   const uint32_t ucid = (LPC == 64) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)cid) : cid;
 
-  T q[E], g[E], p[E], q1[E], p1[E], g1[E];
+  T q[E], g[E], q1[E], p1[E], g1[E];
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     const int i = lane * E + e;
@@ -40,14 +64,17 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
   long long acc = 0;
   constexpr int S = Blk<T>::S;  // one Philox block serves S transitions
   const PhiloxKeys pk = philox_keys(a.seed);  // momentum streams' round keys, in VGPRs
-  // Draw blocks: A = the current block (front = this step), B = the next
-  // one, prefetched. Each wave prefetches on the step whose index matches its
-  // wave phase, so the waves of a SIMD are not all in the Philox/Box-Muller
-  // chain at once and the leapfrogs of the others hide its latency.
+  // Draw blocks: A = the current block, B = the next one, prefetched. The
+  // transition loop below is unrolled over the position k inside a block, so
+  // slot k of A is a fixed register at each place that reads it (nothing is
+  // shifted or indexed at run time). Each wave prefetches at the position
+  // that matches its wave phase, so the waves of a SIMD are not all in the
+  // Philox/Box-Muller chain at once and the leapfrogs of the others hide its
+  // latency. W1: lus[0] holds ln u_k in lane 64-S+k, lus[1..] are unused.
   T zsA[E][S], kesA[S], lusA[S];
   T zsB[E][S], kesB[S], lusB[S];
-  bool hasB = false;
-  const int phase = (int)((gtid >> 6) % S);  // wave index mod S (wave-uniform)
+  // wave index mod S, as a scalar (every lane of a wave has the same value)
+  const int phase = __builtin_amdgcn_readfirstlane((int)((gtid >> 6) % S));
   // the momenta of block blk, their S kinetic energies (S independent
   // reductions) and the S accept log-uniforms
   auto fill = [&](T (&zs)[E][S], T (&kes)[S], T (&lus)[S], uint64_t blk) __attribute__((always_inline)) {
@@ -67,73 +94,61 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
         kp[k] = (e == 0) ? sq : kp[k] + sq;
       }
     }
-    group_sum_n<LPC>(kp);  // 2. kinetic energies, the S sums interleaved
+    // 2. kinetic energies, the S sums interleaved (W1: totals in row 3)
+    if constexpr (W1) group_sum_n_row3(kp);
+    else group_sum_n<LPC>(kp);
 #pragma unroll
     for (int k = 0; k < S; ++k) kes[k] = kp[k] * (T)0.5;
     T us[S];
     uniforms_of(draw_block(a.seed, ucid, blk, TAG_ACC, 0u), us);
-    if constexpr (LPC == 64) {
-      // the S logs of wave-uniform inputs: lane k evaluates ln u_k, one
-      // VALU pass for all S, then each value is read back as a scalar
+    if constexpr (W1) {
+      // the S logs of wave-uniform inputs in one VALU pass: every lane l
+      // evaluates ln u_k for k = l mod S, and lane 64-S+k's copy is the one
+      // the k-th transition's compare reads
       T um = us[0];
 #pragma unroll
       for (int k = 1; k < S; ++k) um = ((lane & (S - 1)) == k) ? us[k] : um;
-      const T lm = glog_unif(um);
-#pragma unroll
-      for (int k = 0; k < S; ++k) lus[k] = lane_k(lm, k);
+      lus[0] = glog_unif(um);
     } else {
 #pragma unroll
       for (int k = 0; k < S; ++k) lus[k] = glog_unif(us[k]);
     }
   };
   const uint64_t st_end = a.step0 + (uint64_t)a.n_steps;
-  // this lane's first sample slot; each stored transition advances it one row
-  // (C*D elements) instead of recomputing the 64-bit row address
-  T* __restrict__ out = (T*)a.samples + (a.sample_row0 * a.C + c) * D + lane * E;
-  const long long row_stride = a.C * D;
+  // the first sample slot; each stored transition advances it one row (C*D
+  // elements) instead of recomputing the 64-bit row address. W1: the chain's
+  // row as a scalar pointer, the lane's offset added by the store itself.
+  const long long cu =
+      W1 ? (long long)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : c;
+  // (D read back as a scalar of its own: the compiler otherwise shares the
+  // 64-bit D of the per-lane state addresses, a vector register pair, and
+  // the whole pointer chain follows it to the vector unit)
+  const long long Du = W1 ? (long long)__builtin_amdgcn_readfirstlane(D) : (long long)D;
+  T* __restrict__ out = (T*)a.samples + (a.sample_row0 * a.C + cu) * Du + (W1 ? 0 : lane * E);
+  const long long row_stride = a.C * Du;
+  const int lfu = LF ? LF : a.lf_unroll;
+  uint32_t soff = (uint32_t)(lane * E * (int)sizeof(T));  // W1: byte offset of this lane's slots in a sample row
 
-  for (int s = 0; s < a.n_steps; ++s) {
-    const uint64_t st = a.step0 + (uint64_t)s;
-    const int k0 = (int)(st % S);
-    if (s == 0 || k0 == 0) {
-      if (s > 0 && hasB) {
-#pragma unroll
-        for (int k = 0; k < S; ++k) {
-#pragma unroll
-          for (int e = 0; e < E; ++e) zsA[e][k] = zsB[e][k];
-          kesA[k] = kesB[k];
-          lusA[k] = lusB[k];
-        }
-      } else {
-        fill(zsA, kesA, lusA, st / S);
-#pragma unroll
-        for (int e = 0; e < E; ++e) skip_front(zsA[e], k0);
-        skip_front(kesA, k0);
-        skip_front(lusA, k0);
-      }
-      hasB = false;
-    }
-    // 1. momentum ~ N(0, I) and its kinetic energy: front of the block
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      p[e] = zsA[e][0];
-      shift_front(zsA[e]);
-    }
-    const T ke0 = kesA[0];
-    const T lnu = lusA[0];
-    shift_front(kesA);
-    shift_front(lusA);
-    // prefetch the next block (if this launch reaches it)
-    if (!hasB && k0 == phase && st - (uint64_t)k0 + S < st_end) {
-      fill(zsB, kesB, lusB, st / S + 1);
-      hasB = true;
-    }
+  int s = 0;             // transitions done
+  uint64_t blk = 0;      // the draw block in A
+  bool more = false;     // this launch reaches block blk + 1
+  bool hasB = false;     // ... and B holds it
+  // the transition at position K of block blk
+  auto step = [&](auto kc) __attribute__((always_inline)) {
+    constexpr int K = decltype(kc)::v;
+    // 1. momentum ~ N(0, I) and its kinetic energy: slot K of the block;
     // 4. proposal buffers
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       q1[e] = q[e];
-      p1[e] = p[e];
+      p1[e] = zsA[e][K];
       g1[e] = g[e];
+    }
+    const T ke0 = kesA[K];
+    // prefetch the next block (if this launch reaches it)
+    if (K == phase && more) {
+      fill(zsB, kesB, lusB, blk + 1);
+      hasB = true;
     }
     // 5. leapfrog: L-1 gradient-only steps, then the last one with logp.
     // The kicks p + g*(eps/2) and the drift q + p*eps are the engine's fused
@@ -155,12 +170,12 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
       for (int e = 0; e < E; ++e) p1[e] = gfma(g1[e], half, p1[e]);
     };
     int l = 0;
-    if (a.lf_unroll == 4)
+    if (lfu == 4)
       for (; l + 4 < a.L; l += 4) { lf(); lf(); lf(); lf(); }
     // two leapfrogs per loop trip at 2-4 waves per SIMD (one taken branch and
     // loop test per two): kernel -1.4 % at the headline's 4 waves per SIMD,
     // but cfg4 at 8 waves per SIMD -4.7 % (profiles/r04/ab_hmc_unroll2.log)
-    if (a.lf_unroll == 2)
+    if (lfu == 2)
       for (; l + 2 < a.L; l += 2) { lf(); lf(); }
     for (; l + 1 < a.L; ++l) lf();
     // 6. proposed kinetic energy, from the in-lane sums of p'^2
@@ -188,7 +203,8 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
 #pragma unroll
           for (int e = 0; e < E; ++e) p1[e] = gfma(g1[e], half, p1[e]);
           sums[1] = kin_part();
-          group_sum_n<LPC>(sums);
+          if constexpr (W1) group_sum_n_row3(sums);
+          else group_sum_n<LPC>(sums);
           lp1 = tg.finish(sums[0]);
           ke1 = sums[1] * (T)0.5;
         } else {
@@ -206,9 +222,13 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
     } else {
       ke1 = group_sum<LPC>(kin_part()) * (T)0.5;
     }
-    // 7-9. Metropolis accept (NaN log_alpha rejects)
+    // 7-9. Metropolis accept (NaN log_alpha rejects). W1: the operands are
+    // the chain's in row 3, lane 64-S+K compares with this transition's ln u
     const T log_alpha = (lp1 - lp) + (ke0 - ke1);
-    if (log_alpha >= lnu) {
+    bool accept;
+    if constexpr (W1) accept = (__builtin_amdgcn_ballot_w64(log_alpha >= lusA[0]) >> (64 - S + K)) & 1;
+    else accept = log_alpha >= lusA[K];
+    if (accept) {
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         q[e] = q1[e];
@@ -221,9 +241,50 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const int i = lane * E + e;
-        if (i < D) out[e] = q[e];
+        // W1: scalar row pointer + this lane's 32-bit byte offset (the saddr
+        // store form). The empty asm on the offset's own register keeps its
+        // zero extension next to the store, where instruction selection can
+        // fold it (hoisted out of the loop it becomes a 64-bit add per row);
+        // in place, so it costs no move.
+        if constexpr (W1) {
+          if (e == 0) asm volatile("" : "+v"(soff));
+          if (i < D) *(T*)((char*)out + soff + e * sizeof(T)) = q[e];
+        } else {
+          if (i < D) out[e] = q[e];
+        }
       }
       out += row_stride;
+    }
+  };
+  // Block by block, the S positions unrolled. A launch may start and end
+  // inside a block (step0 % S, st_end % S): wave-uniform tests skip the
+  // positions before its first and after its last transition.
+  if (a.n_steps > 0) {
+    blk = a.step0 / S;
+    int kb = (int)(a.step0 % S);
+    for (;;) {
+      if (hasB) {
+#pragma unroll
+        for (int k = 0; k < S; ++k) {
+#pragma unroll
+          for (int e = 0; e < E; ++e) zsA[e][k] = zsB[e][k];
+          kesA[k] = kesB[k];
+          if (!W1 || k == 0) lusA[k] = lusB[k];
+        }
+      } else {
+        fill(zsA, kesA, lusA, blk);
+      }
+      hasB = false;
+      more = (blk + 1) * S < st_end;
+      for_each_k<0, S>([&](auto kc) __attribute__((always_inline)) {
+        if (decltype(kc)::v >= kb && s < a.n_steps) {
+          step(kc);
+          ++s;
+        }
+      });
+      if (!more) break;
+      kb = 0;
+      ++blk;
     }
   }
 #pragma unroll
@@ -231,7 +292,8 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
     const int i = lane * E + e;
     if (i < D) qs[c * D + i] = q[e];
   }
-  if (lane == 0) {
+  // W1: lane 63 owns the chain's logp (row 3)
+  if (lane == (W1 ? 63 : 0)) {
     ((T*)a.logp)[c] = lp;
     a.accepts[c] += acc;
   }

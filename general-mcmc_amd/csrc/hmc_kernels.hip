@@ -21,6 +21,9 @@
 #include "gm_layouts.h"
 
 namespace gm {
+hipError_t launch_hmc_f32(const TargetDev& tg, const Layout& lay, const HmcLaunch& a, hipStream_t st, LaunchEvents ev);
+hipError_t launch_hmc_f64(const TargetDev& tg, const Layout& lay, const HmcLaunch& a, hipStream_t st, LaunchEvents ev);
+
 hipError_t launch_hmc(gm_dtype dt, const TargetDev& tg, const Layout& lay, const HmcLaunch& a,
                       hipStream_t st, LaunchEvents ev) {
   if (tg.kind == GM_TARGET_CUSTOM) {  // user target, runtime-compiled (gm_jit.cpp)
@@ -36,16 +39,8 @@ hipError_t launch_hmc(gm_dtype dt, const TargetDev& tg, const Layout& lay, const
       return launch_timed(hmc_wide_kernel<T, E, TG>, dim3((unsigned)a.C), dim3(lay.lanes), 0, st, ev, a, t);
     });
   }
-  // (two chains per wave on packed f32 arithmetic, 13 VALU per two
-  // chain-leapfrogs instead of 22, bitwise equal, measured no faster: at the
-  // 2 waves per SIMD it leaves at 4096 chains the loop is latency-bound,
-  // profiles/r04/ab_hmc_packed_and_fma_order.log; not kept)
-  return dispatch(dt, tg, lay, [&]<class T, int LPC, int E, class TG>(TG t) -> hipError_t {
-    const size_t lds = t.template lds_bytes<LPC, E>();
-    const long long threads = a.C * LPC;
-    const unsigned blocks = (unsigned)((threads + 255) / 256);
-    return launch_timed(hmc_kernel<T, LPC, E, TG>, dim3(blocks), dim3(256), lds, st, ev, a, t);
-  });
+  // the lane-group kernels, one translation unit per dtype (hmc_part.inc)
+  return dt == GM_F32 ? launch_hmc_f32(tg, lay, a, st, ev) : launch_hmc_f64(tg, lay, a, st, ev);
 }
 
 }  // namespace gm

@@ -1,0 +1,37 @@
+// hmc_part.inc — one dtype's slice of the hmc_kernel instantiations (every
+// layout and built-in target), so that the two slices compile in parallel
+// (hmc_f32.hip and hmc_f64.hip define GM_HMC_T and GM_HMC_NAME).
+#include "gm_layouts.h"
+#include "hmc_device.h"
+
+namespace gm {
+hipError_t GM_HMC_NAME(const TargetDev& tg, const Layout& lay, const HmcLaunch& a, hipStream_t st,
+                       LaunchEvents ev) {
+  // (two chains per wave on packed f32 arithmetic, 13 VALU per two
+  // chain-leapfrogs instead of 22, bitwise equal, measured no faster: at the
+  // 2 waves per SIMD it leaves at 4096 chains the loop is latency-bound,
+  // profiles/r04/ab_hmc_packed_and_fma_order.log; not kept)
+  auto f = [&]<class T, int LPC, int E, class TG>(TG t) -> hipError_t {
+    const size_t lds = t.template lds_bytes<LPC, E>();
+    const long long threads = a.C * LPC;
+    const unsigned blocks = (unsigned)((threads + 255) / 256);
+    // one chain per wave with 1 or 2 elements per lane (the many-chain
+    // shapes): the leapfrog loop form is compiled in, so each of the S
+    // unrolled block positions carries one form instead of three
+    if constexpr (LPC == 64 && E <= 2) {
+      if (a.lf_unroll == 4)
+        return launch_timed(hmc_kernel<T, LPC, E, TG, 4>, dim3(blocks), dim3(256), lds, st, ev, a, t);
+      if (a.lf_unroll == 2)
+        return launch_timed(hmc_kernel<T, LPC, E, TG, 2>, dim3(blocks), dim3(256), lds, st, ev, a, t);
+      return launch_timed(hmc_kernel<T, LPC, E, TG, 1>, dim3(blocks), dim3(256), lds, st, ev, a, t);
+    } else {
+      return launch_timed(hmc_kernel<T, LPC, E, TG>, dim3(blocks), dim3(256), lds, st, ev, a, t);
+    }
+  };
+#define GM_TRY_LAYOUT(L_, E_) \
+  if (lay.lanes == L_ && lay.elems == E_) return dispatch_target<GM_HMC_T, L_, E_>(tg, f);
+  GM_LAYOUT_LIST(GM_TRY_LAYOUT)
+#undef GM_TRY_LAYOUT
+  return hipErrorInvalidValue;
+}
+}  // namespace gm
