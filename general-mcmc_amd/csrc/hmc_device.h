@@ -19,6 +19,25 @@ template <int K, int S, class F> __device__ __forceinline__ void for_each_k(F&& 
   }
 }
 
+// One chain per wave: the accept log-uniforms of the 64-transition window that
+// holds draw block blk, lane k's the one of transition 64 w + k (stream
+// TAG_ACC, index 0: block (64 w + k) / S, word k % S, as every transition's
+// own draw). One per-lane Philox and one glog_unif pass serve 64 transitions
+// (as mh_kernel's, mh_device.h); per block, all 64 lanes ran that pass for S
+// distinct values behind a scalar Philox.
+template <class T>
+__device__ __forceinline__ T accept_window(uint64_t seed, uint32_t ucid, uint64_t blk, int lane) {
+  constexpr int S = Blk<T>::S;
+  // the window's first block has its low log2(64 / S) bits clear: no carry
+  const uint64_t lb = (blk & ~(uint64_t)(64 / S - 1)) | (uint64_t)(lane / S);
+  T us[S];
+  uniforms_of(draw_block_v(seed, ucid, lb, TAG_ACC, 0u), us);
+  T um = us[0];
+#pragma unroll
+  for (int k = 1; k < S; ++k) um = ((lane & (S - 1)) == k) ? us[k] : um;
+  return glog_unif(um);
+}
+
 // LF: the leapfrog loop form (1, 2 or 4 leapfrogs per trip) as a constant, or
 // 0 for the launch's a.lf_unroll (all three forms in the code).
 //
@@ -26,10 +45,12 @@ template <int K, int S, class F> __device__ __forceinline__ void for_each_k(F&& 
 // in row 3 of the wave (lanes 48..63, group_sum_n_row3) and everything derived
 // from them (the kinetic energies, log_alpha, the chain's logp) is computed
 // there in the vector registers, without the read of lane 63 into a scalar
-// and back. The block's S accept log-uniforms sit in lanes 64-S..63 of one
-// register, so the decision of the block's k-th transition is bit 64-S+k of
-// one vector compare, and the branch on it is wave-uniform. The accept count
-// and the sample row pointer are then scalars.
+// and back. The accept log-uniforms of the 64 transitions 64 w .. 64 w + 63
+// (a window) sit in the 64 lanes of one register, computed in one VALU pass
+// per window (accept_window); transition st reads lane st % 64 of it as a
+// scalar, the decision is bit 63 of one vector compare with it, and the
+// branch on it is wave-uniform. The accept count and the sample row pointer
+// are then scalars.
 template <class T, int LPC, int E, class TG, int LF = 0>
 __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
   constexpr bool W1 = LPC == 64;
@@ -70,14 +91,22 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
   // shifted or indexed at run time). Each wave prefetches at the position
   // that matches its wave phase, so the waves of a SIMD are not all in the
   // Philox/Box-Muller chain at once and the leapfrogs of the others hide its
-  // latency. W1: lus[0] holds ln u_k in lane 64-S+k, lus[1..] are unused.
+  // latency. W1: the lus are unused; lw is the accept window of block A (lane
+  // k: ln u of transition 64 w + k) and lwN the next window, which the
+  // prefetch of a window's first block computes (at this wave's phase
+  // position like the rest of the block, so the waves of a SIMD do not take
+  // the pass at the same transition) and the A <- B copy of that block hands
+  // over. A launch's first fill computes its whole window, wherever it starts.
   T zsA[E][S], kesA[S], lusA[S];
   T zsB[E][S], kesB[S], lusB[S];
+  T lw = (T)0, lwN = (T)0;
   // wave index mod S, as a scalar (every lane of a wave has the same value)
   const int phase = __builtin_amdgcn_readfirstlane((int)((gtid >> 6) % S));
   // the momenta of block blk, their S kinetic energies (S independent
-  // reductions) and the S accept log-uniforms
-  auto fill = [&](T (&zs)[E][S], T (&kes)[S], T (&lus)[S], uint64_t blk) __attribute__((always_inline)) {
+  // reductions) and the S accept log-uniforms (W1: block blk's window into
+  // win, if `window`)
+  auto fill = [&](T (&zs)[E][S], T (&kes)[S], T (&lus)[S], T& win, bool window, uint64_t blk)
+                  __attribute__((always_inline)) {
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const int i = lane * E + e;
@@ -99,21 +128,17 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
     else group_sum_n<LPC>(kp);
 #pragma unroll
     for (int k = 0; k < S; ++k) kes[k] = kp[k] * (T)0.5;
-    T us[S];
-    uniforms_of(draw_block(a.seed, ucid, blk, TAG_ACC, 0u), us);
     if constexpr (W1) {
-      // the S logs of wave-uniform inputs in one VALU pass: every lane l
-      // evaluates ln u_k for k = l mod S, and lane 64-S+k's copy is the one
-      // the k-th transition's compare reads
-      T um = us[0];
-#pragma unroll
-      for (int k = 1; k < S; ++k) um = ((lane & (S - 1)) == k) ? us[k] : um;
-      lus[0] = glog_unif(um);
+      if (window) win = accept_window<T>(a.seed, ucid, blk, lane);
     } else {
+      T us[S];
+      uniforms_of(draw_block(a.seed, ucid, blk, TAG_ACC, 0u), us);
 #pragma unroll
       for (int k = 0; k < S; ++k) lus[k] = glog_unif(us[k]);
     }
   };
+  // block b is the first of its accept window
+  auto opens_window = [](uint64_t b) { return (b & (uint64_t)(64 / S - 1)) == 0; };
   const uint64_t st_end = a.step0 + (uint64_t)a.n_steps;
   // the first sample slot; each stored transition advances it one row (C*D
   // elements) instead of recomputing the 64-bit row address. W1: the chain's
@@ -147,7 +172,7 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
     const T ke0 = kesA[K];
     // prefetch the next block (if this launch reaches it)
     if (K == phase && more) {
-      fill(zsB, kesB, lusB, blk + 1);
+      fill(zsB, kesB, lusB, lwN, opens_window(blk + 1), blk + 1);
       hasB = true;
     }
     // 5. leapfrog: L-1 gradient-only steps, then the last one with logp.
@@ -223,11 +248,21 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
       ke1 = group_sum<LPC>(kin_part()) * (T)0.5;
     }
     // 7-9. Metropolis accept (NaN log_alpha rejects). W1: the operands are
-    // the chain's in row 3, lane 64-S+K compares with this transition's ln u
+    // the chain's in row 3; this transition's ln u is its lane of the window,
+    // read as a scalar, and lane 63's compare decides
     const T log_alpha = (lp1 - lp) + (ke0 - ke1);
     bool accept;
-    if constexpr (W1) accept = (__builtin_amdgcn_ballot_w64(log_alpha >= lusA[0]) >> (64 - S + K)) & 1;
-    else accept = log_alpha >= lusA[K];
+    if constexpr (W1) {
+      const T lnu = lane_k(lw, (int)(((uint32_t)blk * (uint32_t)S + (uint32_t)K) & 63u));
+      // (bit 31 of the mask's high word, opaque as a scalar: the compiler
+      // turns a test of bit 63 of the 64-bit mask into a signed 64-bit
+      // compare, which only the vector unit has)
+      uint32_t hi = (uint32_t)(__builtin_amdgcn_ballot_w64(log_alpha >= lnu) >> 32);
+      asm volatile("" : "+s"(hi));
+      accept = (hi >> 31) != 0;
+    } else {
+      accept = log_alpha >= lusA[K];
+    }
     if (accept) {
 #pragma unroll
       for (int e = 0; e < E; ++e) {
@@ -269,10 +304,16 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
 #pragma unroll
           for (int e = 0; e < E; ++e) zsA[e][k] = zsB[e][k];
           kesA[k] = kesB[k];
-          if (!W1 || k == 0) lusA[k] = lusB[k];
+          if (!W1) lusA[k] = lusB[k];
+        }
+        if constexpr (W1) {
+          if (opens_window(blk)) lw = lwN;
         }
       } else {
-        fill(zsA, kesA, lusA, blk);
+        // the launch's first block, or the one after a first block that began
+        // past this wave's prefetch position (its window is already in lw
+        // unless it opens a new one)
+        fill(zsA, kesA, lusA, lw, s == 0 || opens_window(blk), blk);
       }
       hasB = false;
       more = (blk + 1) * S < st_end;
