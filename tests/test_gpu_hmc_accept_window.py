@@ -15,7 +15,16 @@ eps = 0.038 was chosen on the CPU with the oracle alone: over the 385
 transitions its accept fraction is 0.76 (f32, D = 64), 0.72 (f32, D = 100)
 and 0.77 (f64, D = 64), every chain between 0.70 and 0.79, so accepted and
 rejected proposals both occur in every window; each case asserts that on the
-oracle's counts."""
+oracle's counts.
+
+The layouts with more than two elements per lane (the kernel's LF = 0 form)
+run the same calls at a padded dim each. At eps = 0.038 the oracle's accept
+fraction is 0.58 (f32, D = 253, 64 x 4; chains 0.51-0.61) and 0.43 (f32,
+D = 509, 64 x 8; chains 0.27-0.48). At f64, D = 1021, 64 x 16 it is 0.23,
+inside the band, but one chain accepts 1 of its 385 proposals (0.003), so its
+windows would hold no accepted proposal; that case runs at eps = 0.03: 0.56,
+every chain between 0.53 and 0.58 (oracle scan: 0.034 gives 0.35 with the
+same chain stuck, 0.028 gives 0.62, 0.024 gives 0.75)."""
 import numpy as np
 import pytest
 
@@ -45,19 +54,21 @@ def test_runs_cover_the_residues_and_lengths():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dtype,dim,lay", [(np.float32, 64, (64, 1)), (np.float32, 100, (64, 2)),
-                                           (np.float64, 64, (64, 1))],
-                         ids=["f32-64x1", "f32-64x2-padded", "f64-64x1"])
-def test_consecutive_launches_equal_one_oracle_run(gm, oracle, dtype, dim, lay):
+@pytest.mark.parametrize("dtype,dim,lay,eps", [(np.float32, 64, (64, 1), EPS), (np.float32, 100, (64, 2), EPS),
+                                               (np.float64, 64, (64, 1), EPS), (np.float32, 253, (64, 4), EPS),
+                                               (np.float32, 509, (64, 8), EPS), (np.float64, 1021, (64, 16), 0.03)],
+                         ids=["f32-64x1", "f32-64x2-padded", "f64-64x1", "f32-64x4-padded", "f32-64x8-padded",
+                              "f64-64x16-padded"])
+def test_consecutive_launches_equal_one_oracle_run(gm, oracle, dtype, dim, lay, eps):
     t = gm.RosenbrockND()
     x0 = (gm.init_with_seed(5, dim, 3, np.float64) * 0.5).astype(dtype)
-    q, ref, acc = oracle.hmc_run(Target.from_product(t, dim), x0, EPS, L, SEED, 0, TOTAL, 0, *lay,
+    q, ref, acc = oracle.hmc_run(Target.from_product(t, dim), x0, eps, L, SEED, 0, TOTAL, 0, *lay,
                                  chain_offset=OFFSET)  # ref: [TOTAL, C, D]
     frac = acc.sum() / (x0.shape[0] * TOTAL)
     print(f"oracle accept fraction {frac:.4f}, per chain {acc / TOTAL}")
     assert 0.2 <= frac <= 0.8
 
-    s = gm.HMC(t, x0, EPS, L, dtype=dtype, chain_offset=OFFSET).set_seed(SEED)
+    s = gm.HMC(t, x0, eps, L, dtype=dtype, chain_offset=OFFSET).set_seed(SEED)
     s.set_layout(*lay)
     assert s.layout() == lay
     step0 = 0
