@@ -80,6 +80,9 @@ SIGNATURES = {
     "gm_hmc_get_step_sizes": (_ip, [_vp, _vp, _vp]),
     "gm_hmc_set_metric": (_ip, [_vp, _vp]),
     "gm_hmc_get_metric": (_ip, [_vp, _vp, _vp]),
+    "gm_hmc_set_dense_adaptation": (_ip, [_vp, _dbl, _i64, _i64, _i64, _dbl, _dbl]),
+    "gm_hmc_set_dense_metric": (_ip, [_vp, _vp]),
+    "gm_hmc_get_dense_metric": (_ip, [_vp, _vp, _vp, _vp, _vp]),
     "gm_mh_create": (_ip, [C.POINTER(gm_target), _ip, _i64, _i64, _vp, _dbl, _i64, C.POINTER(_vp)]),
     "gm_nuts_create": (_ip, [C.POINTER(gm_target), _ip, _i64, _i64, _vp, _dbl, _i32, _i64, C.POINTER(_vp)]),
     "gm_set_seed": (_ip, [_vp, _u64]),

@@ -77,6 +77,27 @@ hipError_t launch_hmc_adapt(gm_dtype dt, const TargetDev& tg, const Layout& lay,
 hipError_t launch_hmc_adapt_window(gm_dtype dt, long long C, int D, double regularize, double jitter,
                                    long long rn, void* eps, const void* eps_bar, void* h_bar, void* mu,
                                    void* dinv, void* dsq, void* rmean, void* rm2, hipStream_t st);
+// per-chain step sizes and one dense metric shared by all chains
+// (hmc_dense_kernels.hip); mode: 0 frozen, 1 step-size adaptation
+// largest dim of the dense metric (Sigma in LDS beside the target's staging;
+// single-workgroup window kernel)
+constexpr int GM_DENSE_MAX_DIM = 64;
+hipError_t launch_hmc_dense(gm_dtype dt, const TargetDev& tg, const Layout& lay, const HmcDenseLaunch& a,
+                            int mode, hipStream_t st, LaunchEvents ev = {});
+// pooled warm-up statistics of x [rows][C][D] in float64: the pivot c0 (mean
+// over chains of row 0), then s1 += sum (x - c0), S2 += sum (x - c0)(x - c0)^T
+// row after row; part: hmc_dense_gram_part_bytes(C, rows) bytes of scratch
+size_t hmc_dense_gram_part_bytes(long long C, int rows);
+hipError_t launch_hmc_dense_pivot(gm_dtype dt, const void* x, long long C, int D, double* c0, hipStream_t st);
+hipError_t launch_hmc_dense_gram(gm_dtype dt, const void* x, int rows, long long C, int D, const double* c0,
+                                 double* part, double* s1, double* S2, hipStream_t st);
+// Sigma (from the statistics, or sig_in), its Cholesky factor and A = L^-T,
+// float64 masters and sampler-dtype copies; statistics reset; restart of the
+// dual averaging (one workgroup)
+hipError_t launch_hmc_dense_window(gm_dtype dt, int D, long long C, int from_stats, long long n, double reg,
+                                   double jitter, double* s1, double* S2, const double* sig_in, double* minv64,
+                                   double* a64, void* minvT, void* atT, long long* counters, int count, int restart,
+                                   void* eps, const void* eps_bar, void* h_bar, void* mu, hipStream_t st);
 
 // ---- run_progress statistics (gm_track.h, tracker_kernels.hip) -------------
 // ChainTracker::new for every chain from the current positions

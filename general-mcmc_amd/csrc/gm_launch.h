@@ -58,6 +58,40 @@ struct HmcAdaptLaunch {
   long long sb = 0, lim = 0;    // Welford collects while sb < m < lim (lim = n_discard - end_buffer)
 };
 
+// ---- HMC with per-chain step sizes and one dense metric for all chains --------
+// (hmc_dense_device.h). A launch is wholly frozen (MODE 0) or wholly warm-up
+// (MODE 1: step-size dual averaging); the pooled statistics are taken from
+// the positions a warm-up launch stores through h.samples.
+struct HmcDenseLaunch {
+  HmcLaunch h;                  // as for the plain kernel (h.eps and h.zs unused)
+  void* eps = nullptr;          // [C] per-chain step size, in/out while adapting
+  void* eps_bar = nullptr;      // [C] in/out (MODE 1)
+  void* h_bar = nullptr;        // [C] in/out (MODE 1)
+  const void* mu = nullptr;     // [C]
+  const void* minv = nullptr;   // [D][D] M^-1 = Sigma (symmetric), sampler dtype
+  const void* at = nullptr;     // [D][D] at[j*D + i] = A_ij, A = L^-T upper triangular (zeros below)
+  double delta = 0.8;           // target acceptance
+  long long k0 = 0;             // dual-averaging restart counter before this launch
+};
+// hmc_dense_kernel's workgroup stays within 64 KiB of LDS: its static part
+// (the f32 Box-Muller tables, 3 KiB; the f64 kernels do not use them and the
+// compiler drops them there, but one rule serves both dtypes) plus at most
+// HMC_DENSE_LDS_DYN bytes of dynamic LDS (target staging, Sigma, slots).
+constexpr int HMC_DENSE_LDS_STATIC = 3072;
+constexpr int HMC_DENSE_LDS_DYN = 64 * 1024 - HMC_DENSE_LDS_STATIC;
+// A user target runs the kernel one chain per lane, layout (1, D): its dynamic
+// LDS is Sigma [D][D] and one slot [D] per thread. The block is the largest of
+// 256, 128, 64, 32 threads that fits (D <= 64: 32 threads always do).
+constexpr unsigned long long hmc_dense_lds_user(int D, int block, int esz) {
+  return ((unsigned long long)D * D + (unsigned long long)block * D) * esz;
+}
+constexpr unsigned hmc_dense_user_block(int D, int esz) {
+  return hmc_dense_lds_user(D, 256, esz) <= HMC_DENSE_LDS_DYN   ? 256u
+         : hmc_dense_lds_user(D, 128, esz) <= HMC_DENSE_LDS_DYN ? 128u
+         : hmc_dense_lds_user(D, 64, esz) <= HMC_DENSE_LDS_DYN  ? 64u
+                                                                : 32u;
+}
+
 // ---- MH --------------------------------------------------------------------
 struct MhLaunch {
   void* q = nullptr;

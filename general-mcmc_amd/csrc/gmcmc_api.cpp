@@ -200,6 +200,26 @@ struct HmcAdapt {
   void *dinv = nullptr, *dsq = nullptr, *rmean = nullptr, *rm2 = nullptr;         // [C][D]
 };
 
+// One dense metric shared by all chains (gm_hmc_set_dense_*;
+// hmc_dense_device.h). `on`: the sampler runs hmc_dense_kernel. The per-chain
+// step sizes, the dual-averaging state, the window configuration and the
+// counters k / rn (here: rows of pooled positions in the open window) are
+// HmcAdapt's, which a dense-metric sampler always has.
+struct HmcDense {
+  bool on = false;
+  double *minv = nullptr, *afac = nullptr;            // [D][D] float64 masters: Sigma, A = L^-T (row-major)
+  double *c0 = nullptr, *s1 = nullptr, *S2 = nullptr;  // pooled statistics: pivot [D], sums [D], [D][D]
+  double* sig_in = nullptr;                            // [D][D] staging of gm_hmc_set_dense_metric
+  void *minv_t = nullptr, *at_t = nullptr;             // sampler-dtype copies (at_t[j*D + i] = A_ij)
+  long long* counters = nullptr;                       // [2] metric updates, failed factorisations
+  void* slab = nullptr;                                // [rows][C][D] warm-up positions of one launch
+  size_t slab_bytes = 0;
+  void* part = nullptr;                                // gram partials
+  size_t part_bytes = 0;
+};
+// the slab's bound (GM_DENSE_MAX_DIM: gm_internal.h)
+constexpr size_t GM_DENSE_SLAB_BYTES = 64u << 20;
+
 struct gm_sampler {
   int kind = 0;
   gm_dtype dt = GM_F32;
@@ -245,6 +265,7 @@ struct gm_sampler {
   long long last_rows = 0;    // sample rows produced by the last run
   NutsState nuts;
   HmcAdapt ha;
+  HmcDense hd;
   // run_progress statistics: per-chain trackers (MH, NUTS) and a
   // MultiChainTracker (HMC), one allocation each (TrackSet)
   void* d_trk = nullptr;
@@ -418,6 +439,103 @@ static int hmc_adapt_callable(gm_sampler* s) {
   return GM_OK;
 }
 
+// ---- HMC dense metric shared by all chains (HmcDense) -----------------------
+static void hmc_dense_free(gm_sampler* s) {
+  HmcDense& d = s->hd;
+  for (void** p : {(void**)&d.minv, (void**)&d.afac, (void**)&d.c0, (void**)&d.s1, (void**)&d.S2,
+                   (void**)&d.sig_in, &d.minv_t, &d.at_t, (void**)&d.counters, &d.slab, &d.part}) {
+    if (*p) hipFree(*p);
+    *p = nullptr;
+  }
+  d = HmcDense();
+}
+
+// The shapes the dense metric takes: an HMC sampler (GM_ESTATE otherwise) on a
+// target with 2 <= dim <= 64 at the dim's default layout: next_pow2(dim) x 1
+// for a built-in target, 1 x dim (the only one) for a user target.
+static int hmc_dense_callable(gm_sampler* s) {
+  GM_REQ(s, "sampler is NULL");
+  if (s->kind != K_HMC) {
+    set_error("the dense metric and its warm-up are for HMC samplers");
+    return GM_ESTATE;
+  }
+  GM_REQ(s->D >= 2 && s->D <= GM_DENSE_MAX_DIM, "the dense metric takes 2 <= dim <= 64");
+  const Layout def = default_layout(s->D, s->dt, s->tg.kind);
+  GM_REQ(s->lay.lanes == def.lanes && s->lay.elems == def.elems,
+         "the dense metric runs at the dim's default layout (next_pow2(dim) x 1) only");
+  return GM_OK;
+}
+
+// sampler-dtype copies of the float64 masters (host arrays, row-major):
+// minv_t = Sigma, at_t[j*D + i] = A_ij; the rounding of the window kernel
+static int hmc_dense_put_copies(gm_sampler* s, const double* minv, const double* afac) {
+  const size_t D = (size_t)s->D;
+  std::vector<double> at(D * D);
+  for (size_t i = 0; i < D; ++i)
+    for (size_t j = 0; j < D; ++j) at[j * D + i] = afac[i * D + j];
+  int rc = put_as(s->dt, minv, D * D, s->hd.minv_t);
+  if (!rc) rc = put_as(s->dt, at.data(), D * D, s->hd.at_t);
+  return rc;
+}
+
+// Allocates the dense state in its start state (Sigma = A = I, no statistics,
+// counters zero) on top of the per-chain arrays; any per-chain diagonal metric
+// is dropped, the step sizes stay. From here on the sampler runs
+// hmc_dense_kernel. The caller has checked hmc_dense_callable.
+static int hmc_dense_ensure(gm_sampler* s) {
+  HmcDense& d = s->hd;
+  if (d.on) return GM_OK;
+  if (s->tg.kind == GM_TARGET_CUSTOM) {  // a source that does not compile for this kernel fails here
+    for (JitKernel jk : {JIT_HMC_DENSE0, JIT_HMC_DENSE1}) {
+      const int rc = jit_prepare(jk, s->dt, s->tg);
+      if (rc) return rc;
+    }
+  }
+  int rc = hmc_adapt_ensure(s);
+  if (rc) return rc;
+  const size_t D = (size_t)s->D, DD = D * D, CD = (size_t)s->C * D;
+  hipError_t e = hipSuccess;
+  for (double** p : {&d.minv, &d.afac, &d.S2, &d.sig_in})
+    if (e == hipSuccess) e = hipMalloc((void**)p, DD * 8);
+  for (double** p : {&d.c0, &d.s1})
+    if (e == hipSuccess) e = hipMalloc((void**)p, D * 8);
+  for (void** p : {&d.minv_t, &d.at_t})
+    if (e == hipSuccess) e = hipMalloc(p, DD * s->esz);
+  if (e == hipSuccess) e = hipMalloc((void**)&d.counters, 2 * sizeof(long long));
+  if (e == hipSuccess) e = hipMemset(d.counters, 0, 2 * sizeof(long long));
+  if (e == hipSuccess) e = hipMemset(d.S2, 0, DD * 8);
+  if (e == hipSuccess) e = hipMemset(d.sig_in, 0, DD * 8);
+  if (e == hipSuccess) e = hipMemset(d.c0, 0, D * 8);
+  if (e == hipSuccess) e = hipMemset(d.s1, 0, D * 8);
+  // the per-chain diagonal metric goes: identity, no Welford statistics
+  if (e == hipSuccess) e = hipMemset(s->ha.rmean, 0, CD * s->esz);
+  if (e == hipSuccess) e = hipMemset(s->ha.rm2, 0, CD * s->esz);
+  if (e != hipSuccess) {
+    hmc_dense_free(s);
+    set_error(std::string("dense metric state allocation failed: ") + hipGetErrorString(e));
+    return GM_ENOMEM;
+  }
+  std::vector<double> eye(DD, 0.0), ones(CD, 1.0);
+  for (size_t i = 0; i < D; ++i) eye[i * D + i] = 1.0;
+  e = hipMemcpy(d.minv, eye.data(), DD * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d.afac, eye.data(), DD * 8, hipMemcpyHostToDevice);
+  rc = e == hipSuccess ? GM_OK : GM_EHIP;
+  if (rc) set_error(std::string("dense metric state setup failed: ") + hipGetErrorString(e));
+  if (!rc) rc = hmc_dense_put_copies(s, eye.data(), eye.data());
+  if (!rc) rc = put_as(s->dt, ones.data(), CD, s->ha.dinv);
+  if (!rc) rc = put_as(s->dt, ones.data(), CD, s->ha.dsq);
+  if (rc) {
+    const std::string msg = gm_last_error();
+    hmc_dense_free(s);
+    set_error(msg);
+    return rc;
+  }
+  s->ha.mode = 0;
+  s->ha.armed = false;
+  d.on = true;
+  return GM_OK;
+}
+
 int gm::build_target(const gm_target* t, gm_dtype dt, long long dim, TargetDev* out, void** d_mu,
                      void** d_prec) {
   GM_REQ(t != nullptr, "target is NULL");
@@ -507,10 +625,11 @@ int gm_custom_target_check(const char* source, gm_dtype dtype, int64_t dim, int3
   GM_REQ(source, "source is NULL");
   GM_REQ(dtype == GM_F32 || dtype == GM_F64, "bad dtype");
   GM_REQ(dim >= 1 && dim <= GM_CUSTOM_MAX_DIM, "CUSTOM targets support dim in [1, 256]");
-  GM_REQ(kind >= 0 && kind <= 4, "kind: 0 logp/grad, 1 HMC, 2 MH, 3 NUTS, 4 HMC warm-up");
-  // 4: hmc_adapt_kernel in its most general instantiation (MODE 2)
+  GM_REQ(kind >= 0 && kind <= 5, "kind: 0 logp/grad, 1 HMC, 2 MH, 3 NUTS, 4 HMC warm-up, 5 HMC dense metric");
+  GM_REQ(kind != 5 || (dim >= 2 && dim <= GM_DENSE_MAX_DIM), "the dense metric takes 2 <= dim <= 64");
+  // 4, 5: hmc_adapt_kernel (MODE 2) and hmc_dense_kernel (MODE 1) in their most general instantiations
   const JitKernel jk = kind == 1 ? JIT_HMC : kind == 2 ? JIT_MH : kind == 3 ? JIT_NUTS
-                       : kind == 4 ? JIT_HMC_ADAPT2 : JIT_LOGP;
+                       : kind == 4 ? JIT_HMC_ADAPT2 : kind == 5 ? JIT_HMC_DENSE1 : JIT_LOGP;
   return jit_compile(jk, dtype, source, (int)dim);
 }
 
@@ -755,6 +874,8 @@ int gm_sampler_layout(gm_sampler* s, int32_t* lanes, int32_t* elems) {
 
 int gm_sampler_set_layout(gm_sampler* s, int32_t lanes, int32_t elems) {
   GM_REQ(s, "sampler is NULL");
+  GM_REQ(!s->hd.on || (lanes == s->lay.lanes && elems == s->lay.elems),
+         "a dense-metric sampler (gm_hmc_set_dense_*) runs at the dim's default layout only");
   GM_REQ(s->tg.kind != GM_TARGET_CUSTOM || (lanes == 1 && elems == s->D),
          "CUSTOM targets run one chain per lane (layout 1 x dim)");
   if (s->tg.kind == GM_TARGET_CUSTOM) return GM_OK;
@@ -873,6 +994,8 @@ static int ensure_run_events(gm_sampler* s) {
 // within this call) are stored at sample rows (index - collect_from).
 static int run_hmc_adapt(gm_sampler* s, long long total, long long collect_from, const StepHook* hook,
                          long long chunk, int lf_unroll, long long warm);
+static int run_hmc_dense(gm_sampler* s, long long total, long long collect_from, const StepHook* hook,
+                         long long chunk, int lf_unroll, long long warm);
 
 static int run_steps(gm_sampler* s, long long total, long long collect_from, int progress,
                      const TrackLaunch* trk = nullptr, const StepHook* hook = nullptr,
@@ -902,6 +1025,7 @@ static int run_steps(gm_sampler* s, long long total, long long collect_from, int
                                                              : hmc_lf_unroll((s->C * s->lay.lanes + 63) / 64);
   if (s->kind == K_HMC && s->ha.has) {
     const long long warm = s->ha.armed && s->ha.mode ? std::min(pending_warm, total) : 0;
+    if (s->hd.on) return run_hmc_dense(s, total, collect_from, hook, chunk, lf_unroll, warm);
     return run_hmc_adapt(s, total, collect_from, hook, chunk, lf_unroll, warm);
   }
   for (long long start = 0; start < total; start += chunk) {
@@ -977,6 +1101,25 @@ static int run_steps(gm_sampler* s, long long total, long long collect_from, int
   return GM_OK;
 }
 
+// The metric windows' ends of an HMC warm-up of `warm` transitions, by
+// transition index m: the NUTS schedule (nuts_run / nuts_set_mass) over
+// sb < m < lim = warm - eb. One schedule for the diagonal (run_hmc_adapt,
+// mode 2) and the dense (run_hmc_dense) warm-up.
+static std::vector<long long> hmc_window_ends(const HmcAdapt& h, long long warm, long long lim) {
+  std::vector<long long> wends;
+  long long sched_len = h.iw > 10 ? h.iw : 10;
+  long long sched_next = (h.sb > 1 ? h.sb : 1) + sched_len;
+  for (long long m = 1; m <= warm; ++m) {
+    if (m <= h.sb || !(m < lim)) continue;
+    if (m >= sched_next || m + 1 >= lim) {
+      sched_next += sched_len;
+      sched_len = sched_len * 2 < 400 ? sched_len * 2 : 400;
+      wends.push_back(m);
+    }
+  }
+  return wends;
+}
+
 // The HMC run of a sampler with per-chain step sizes / metric: the first
 // `warm` transitions are the warm-up (MODE 1 or 2 launches, cut at every
 // window end, where hmc_adapt_window_kernel runs on the stream, and at the
@@ -985,21 +1128,9 @@ static int run_steps(gm_sampler* s, long long total, long long collect_from, int
 static int run_hmc_adapt(gm_sampler* s, long long total, long long collect_from, const StepHook* hook,
                          long long chunk, int lf_unroll, long long warm) {
   HmcAdapt& h = s->ha;
-  // window ends of the NUTS schedule (nuts_run / nuts_set_mass), by transition index m
-  std::vector<long long> wends;
   const long long lim = warm > h.eb ? warm - h.eb : 0;
-  if (warm > 0 && h.mode == 2) {
-    long long sched_len = h.iw > 10 ? h.iw : 10;
-    long long sched_next = (h.sb > 1 ? h.sb : 1) + sched_len;
-    for (long long m = 1; m <= warm; ++m) {
-      if (m <= h.sb || !(m < lim)) continue;
-      if (m >= sched_next || m + 1 >= lim) {
-        sched_next += sched_len;
-        sched_len = sched_len * 2 < 400 ? sched_len * 2 : 400;
-        wends.push_back(m);
-      }
-    }
-  }
+  std::vector<long long> wends;
+  if (h.mode == 2) wends = hmc_window_ends(h, warm, lim);
   size_t wi = 0;
   long long n_launch = 0;
   for (long long pos = 0; pos < total;) {
@@ -1069,6 +1200,137 @@ static int run_hmc_adapt(gm_sampler* s, long long total, long long collect_from,
         e = hipMemcpyAsync(h.eps, h.eps_bar, (size_t)s->C * s->esz, hipMemcpyDeviceToDevice, s->stream);
         h.armed = false;
       }
+    }
+    if (e != hipSuccess) {
+      set_error(std::string("kernel launch failed: ") + hipGetErrorString(e));
+      return GM_EHIP;
+    }
+    ++n_launch;
+    if (hook && *hook) {
+      const int rc = (*hook)(pos + n);
+      if (rc) return rc;
+    }
+    pos += n;
+  }
+  s->step += total;
+  s->total_steps += total;
+  if (!(s->async_runs && s->may_async)) GM_HIP(hipStreamSynchronize(s->stream));
+  s->last_ms_pending = true;
+  s->last_launches = n_launch;
+  return GM_OK;
+}
+
+// The HMC run of a dense-metric sampler: as run_hmc_adapt, with MODE 1
+// launches during the warm-up. While a window is open (sb < m < lim) the
+// launch stores its post-accept positions to the scratch slab through the
+// sample-store path (a warm-up launch collects nothing else), bounded by the
+// slab; after it the pooled statistics take the slab's rows on the stream
+// (pivot at the window's first row, then Gram partials and their fixed-order
+// reduction), and at a window end hmc_dense_window_kernel replaces the metric.
+// Nothing here waits for the device.
+static int run_hmc_dense(gm_sampler* s, long long total, long long collect_from, const StepHook* hook,
+                         long long chunk, int lf_unroll, long long warm) {
+  HmcAdapt& h = s->ha;
+  HmcDense& d = s->hd;
+  const long long lim = warm > h.eb ? warm - h.eb : 0;
+  const std::vector<long long> wends = hmc_window_ends(h, warm, lim);
+  const size_t row_bytes = (size_t)s->C * s->D * s->esz;
+  const long long slab_rows = std::max<long long>(1, (long long)(GM_DENSE_SLAB_BYTES / row_bytes));
+  // gram row batches whose partials stay within 16 MiB
+  const long long rb = std::max<long long>(1, (16LL << 20) / (long long)hmc_dense_gram_part_bytes(s->C, 1));
+  if (warm > 0 && lim - 1 > h.sb) {  // both scratch buffers once, before anything is enqueued
+    const long long rows = std::min(std::min(slab_rows, chunk), lim - 1 - h.sb);
+    int rc = ensure_buf(&d.slab, &d.slab_bytes, (size_t)rows * row_bytes);
+    if (!rc) rc = ensure_buf(&d.part, &d.part_bytes, hmc_dense_gram_part_bytes(s->C, (int)std::min(rb, rows)));
+    if (rc) return rc;
+  }
+  size_t wi = 0;
+  long long n_launch = 0;
+  for (long long pos = 0; pos < total;) {
+    long long n = total - pos < chunk ? total - pos : chunk;
+    const bool in_warm = pos < warm;
+    bool upd = false;
+    long long cf = collect_from - pos;
+    if (cf < 0) cf = 0;
+    if (cf > n) cf = n;
+    long long row0 = pos - collect_from;
+    if (row0 < 0) row0 = 0;
+    long long used = 0;  // rows of this launch that enter the pooled statistics
+    if (in_warm) {
+      if (n > warm - pos) n = warm - pos;
+      // transitions m = pos + s + 1 with sb < m < lim are stored from s = cf
+      const long long first = std::max(pos + 1, h.sb + 1);
+      if (first < lim && first <= pos + n) {
+        cf = first - pos - 1;
+        if (n > cf + slab_rows) n = cf + slab_rows;
+        if (n > lim - 1 - pos) n = lim - 1 - pos;  // nothing past the last window is stored
+      } else {
+        cf = n;
+      }
+      if (wi < wends.size() && wends[wi] <= pos + n) {  // cut at the window end (transition m = pos + n)
+        n = wends[wi] - pos;
+        upd = true;
+        ++wi;
+      }
+      if (cf > n) cf = n;
+      row0 = 0;
+      const long long hi = std::min(pos + n, lim - 1);
+      used = hi >= first ? hi - first + 1 : 0;
+    }
+    LaunchEvents ev;
+    if (pos == 0) ev.start = s->evs[0];
+    if (pos + n >= total) ev.stop = s->evs[1];
+    HmcDenseLaunch a;
+    a.h.q = s->d_q;
+    a.h.logp = s->d_logp;
+    a.h.accepts = s->d_acc;
+    a.h.samples = in_warm ? d.slab : s->d_samples;
+    a.h.C = s->C;
+    a.h.D = s->D;
+    a.h.eps = s->eps;
+    a.h.L = s->L;
+    a.h.seed = s->seed;
+    a.h.step0 = s->step + pos;
+    a.h.chain_offset = s->chain_offset;
+    a.h.n_steps = (int)n;
+    a.h.collect_from = (int)cf;
+    a.h.sample_row0 = row0;
+    a.h.lf_unroll = lf_unroll;
+    a.eps = h.eps;
+    a.eps_bar = h.eps_bar;
+    a.h_bar = h.h_bar;
+    a.mu = h.mu;
+    a.minv = d.minv_t;
+    a.at = d.at_t;
+    a.delta = h.delta;
+    a.k0 = h.k;
+    // the run's stop event goes after the statistics when this launch has some
+    LaunchEvents kev = ev;
+    if (in_warm) kev.stop = nullptr;
+    hipError_t e = launch_hmc_dense(s->dt, s->tg, s->lay, a, in_warm ? 1 : 0, s->stream, kev);
+    if (e == hipSuccess && in_warm) {
+      h.k += n;
+      if (used > 0) {
+        if (h.rn == 0) e = launch_hmc_dense_pivot(s->dt, d.slab, s->C, s->D, d.c0, s->stream);
+        for (long long r = 0; r < used && e == hipSuccess; r += rb) {
+          const int rows = (int)std::min(rb, used - r);
+          e = launch_hmc_dense_gram(s->dt, (const char*)d.slab + (size_t)r * row_bytes, rows, s->C, s->D, d.c0,
+                                    (double*)d.part, d.s1, d.S2, s->stream);
+        }
+        h.rn += used;
+      }
+      if (e == hipSuccess && upd && h.rn >= 5) {  // (fewer than 5 rows: nothing changes, the statistics are kept)
+        e = launch_hmc_dense_window(s->dt, s->D, s->C, 1, h.rn * s->C, h.reg, h.jit, d.s1, d.S2, d.sig_in, d.minv,
+                                    d.afac, d.minv_t, d.at_t, d.counters, 1, 1, h.eps, h.eps_bar, h.h_bar, h.mu,
+                                    s->stream);
+        h.k = 0;
+        h.rn = 0;
+      }
+      if (e == hipSuccess && pos + n == warm) {  // the warm-up is over: eps = eps_bar, frozen from here on
+        e = hipMemcpyAsync(h.eps, h.eps_bar, (size_t)s->C * s->esz, hipMemcpyDeviceToDevice, s->stream);
+        h.armed = false;
+      }
+      if (e == hipSuccess && ev.stop) e = hipEventRecord(ev.stop, s->stream);
     }
     if (e != hipSuccess) {
       set_error(std::string("kernel launch failed: ") + hipGetErrorString(e));
@@ -1437,6 +1699,7 @@ int gm_hmc_set_adaptation(gm_sampler* s, int32_t mode, double target_accept, int
   GM_HIP(hipSetDevice(s->device));
   GM_HIP(hipStreamSynchronize(s->stream));
   if (mode == 0) {  // back to the scalar step size, the identity metric and hmc_kernel
+    hmc_dense_free(s);
     hmc_adapt_free(s);
     return GM_OK;
   }
@@ -1454,6 +1717,9 @@ int gm_hmc_set_adaptation(gm_sampler* s, int32_t mode, double target_accept, int
     rc = jit_prepare(mode == 1 ? JIT_HMC_ADAPT1 : JIT_HMC_ADAPT2, s->dt, s->tg);
     if (rc) return rc;
   }
+  // every check has passed: a dense metric (gm_hmc_set_dense_*) goes first;
+  // the per-chain arrays under it stay, with the identity diagonal metric
+  hmc_dense_free(s);
   rc = hmc_adapt_ensure(s);
   if (rc) return rc;
   HmcAdapt& h = s->ha;
@@ -1522,6 +1788,10 @@ int gm_hmc_get_step_sizes(gm_sampler* s, double* eps, double* eps_bar) {
 int gm_hmc_set_metric(gm_sampler* s, const void* diag_inv) {
   int rc = hmc_adapt_callable(s);
   if (rc) return rc;
+  if (s->hd.on) {
+    set_error("the sampler has a dense metric (gm_hmc_set_dense_*): no per-chain diagonal metric");
+    return GM_ESTATE;
+  }
   GM_REQ(diag_inv, "diag_inv is NULL");
   const size_t n = (size_t)s->C * s->D;
   // checked in full before anything changes; sqrt(M) = 1/sqrt(M^-1) in the sampler dtype
@@ -1549,6 +1819,10 @@ int gm_hmc_set_metric(gm_sampler* s, const void* diag_inv) {
 int gm_hmc_get_metric(gm_sampler* s, void* diag_inv, void* diag_sqrt) {
   int rc = hmc_adapt_callable(s);
   if (rc) return rc;
+  if (s->hd.on) {
+    set_error("the sampler has a dense metric (gm_hmc_get_dense_metric): no per-chain diagonal metric");
+    return GM_ESTATE;
+  }
   const size_t n = (size_t)s->C * s->D;
   if (!s->ha.has) {
     for (void* o : {diag_inv, diag_sqrt}) {
@@ -1564,6 +1838,109 @@ int gm_hmc_get_metric(gm_sampler* s, void* diag_inv, void* diag_sqrt) {
   GM_HIP(hipStreamSynchronize(s->stream));
   if (diag_inv) GM_HIP(hipMemcpy(diag_inv, s->ha.dinv, n * s->esz, hipMemcpyDeviceToHost));
   if (diag_sqrt) GM_HIP(hipMemcpy(diag_sqrt, s->ha.dsq, n * s->esz, hipMemcpyDeviceToHost));
+  return GM_OK;
+}
+
+int gm_hmc_set_dense_adaptation(gm_sampler* s, double target_accept, int64_t start_buffer, int64_t end_buffer,
+                                int64_t initial_window, double regularize, double jitter) {
+  int rc = hmc_dense_callable(s);
+  if (rc) return rc;
+  GM_REQ(target_accept > 0 && target_accept < 1, "target_accept must be in (0, 1)");
+  GM_REQ(start_buffer >= 0 && end_buffer >= 0 && initial_window >= 0, "window sizes must be >= 0");
+  GM_REQ(regularize >= 0 && regularize <= 1, "regularize must be in [0, 1]");
+  GM_REQ(!std::isnan(jitter), "jitter is NaN");
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  const size_t C = (size_t)s->C, D = (size_t)s->D;
+  std::vector<double> e(C, hmc_eps_rounded(s)), mu(C);
+  if (s->ha.has) {
+    rc = get_as(s->dt, s->ha.eps, C, e.data());
+    if (rc) return rc;
+  }
+  for (size_t c = 0; c < C; ++c) {
+    GM_REQ(e[c] > 0 && std::isfinite(e[c]), "step sizes must be finite and > 0 to be adapted");
+    mu[c] = std::log(10.0 * e[c]);
+  }
+  rc = hmc_dense_ensure(s);
+  if (rc) return rc;
+  HmcAdapt& h = s->ha;
+  HmcDense& d = s->hd;
+  // start state: eps_bar = eps, mu = ln(10 eps), h_bar = 0, k = 0, no statistics; the metric stays
+  GM_HIP(hipMemcpy(h.eps_bar, h.eps, C * s->esz, hipMemcpyDeviceToDevice));
+  rc = put_as(s->dt, mu.data(), C, h.mu);
+  if (rc) return rc;
+  GM_HIP(hipMemset(h.h_bar, 0, C * s->esz));
+  GM_HIP(hipMemset(d.c0, 0, D * 8));
+  GM_HIP(hipMemset(d.s1, 0, D * 8));
+  GM_HIP(hipMemset(d.S2, 0, D * D * 8));
+  h.mode = 1;  // the kernel's MODE while warming up; the windows are run_hmc_dense's
+  h.armed = true;
+  h.delta = target_accept;
+  h.sb = start_buffer;
+  h.eb = end_buffer;
+  h.iw = initial_window;
+  h.reg = regularize;
+  h.jit = jitter;
+  h.k = 0;
+  h.rn = 0;
+  return GM_OK;
+}
+
+int gm_hmc_set_dense_metric(gm_sampler* s, const double* minv) {
+  int rc = hmc_dense_callable(s);
+  if (rc) return rc;
+  GM_REQ(minv, "minv is NULL");
+  const size_t D = (size_t)s->D;
+  // checked in full before anything changes: finite, symmetric, and positive
+  // definite by the factorisation the window kernel runs (same operations)
+  for (size_t i = 0; i < D * D; ++i) GM_REQ(std::isfinite(minv[i]), "minv entries must be finite");
+  for (size_t i = 0; i < D; ++i)
+    for (size_t j = 0; j < i; ++j) GM_REQ(minv[i * D + j] == minv[j * D + i], "minv must be symmetric");
+  {
+    std::vector<double> l(minv, minv + D * D);
+    for (size_t k = 0; k < D; ++k) {
+      const double piv = l[k * D + k];
+      GM_REQ(piv > 0 && std::isfinite(piv), "minv must be positive definite");
+      const double lkk = std::sqrt(piv);
+      for (size_t i = k + 1; i < D; ++i) l[i * D + k] = l[i * D + k] / lkk;
+      for (size_t i = k + 1; i < D; ++i)
+        for (size_t j = k + 1; j <= i; ++j) l[i * D + j] = l[i * D + j] - l[i * D + k] * l[j * D + k];
+    }
+  }
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  rc = hmc_dense_ensure(s);
+  if (rc) return rc;
+  HmcAdapt& h = s->ha;
+  HmcDense& d = s->hd;
+  GM_HIP(hipMemcpy(d.sig_in, minv, D * D * 8, hipMemcpyHostToDevice));
+  // factored by the kernel that factors an adapted metric; counters and warm-up state untouched
+  hipError_t e = launch_hmc_dense_window(s->dt, s->D, s->C, 0, 0, 0.0, 0.0, d.s1, d.S2, d.sig_in, d.minv, d.afac,
+                                         d.minv_t, d.at_t, d.counters, 0, 0, h.eps, h.eps_bar, h.h_bar, h.mu,
+                                         s->stream);
+  if (e != hipSuccess) {
+    set_error(std::string("kernel launch failed: ") + hipGetErrorString(e));
+    return GM_EHIP;
+  }
+  GM_HIP(hipStreamSynchronize(s->stream));
+  return GM_OK;
+}
+
+int gm_hmc_get_dense_metric(gm_sampler* s, double* minv, double* a_factor, int64_t* updates, int64_t* failed) {
+  GM_REQ(s, "sampler is NULL");
+  if (s->kind != K_HMC || !s->hd.on) {
+    set_error("the sampler has no dense metric (gm_hmc_set_dense_adaptation / gm_hmc_set_dense_metric)");
+    return GM_ESTATE;
+  }
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  const size_t DD = (size_t)s->D * s->D;
+  if (minv) GM_HIP(hipMemcpy(minv, s->hd.minv, DD * 8, hipMemcpyDeviceToHost));
+  if (a_factor) GM_HIP(hipMemcpy(a_factor, s->hd.afac, DD * 8, hipMemcpyDeviceToHost));
+  long long cnt[2] = {0, 0};
+  GM_HIP(hipMemcpy(cnt, s->hd.counters, sizeof(cnt), hipMemcpyDeviceToHost));
+  if (updates) *updates = cnt[0];
+  if (failed) *failed = cnt[1];
   return GM_OK;
 }
 
@@ -1724,6 +2101,15 @@ std::vector<StatePart> state_parts_for(gm_sampler* s, int mass_mode) {
     for (void* p : {h.eps, h.eps_bar, h.h_bar, h.mu}) v.push_back({p, C * e});
     for (void* p : {h.dinv, h.dsq, h.rmean, h.rm2}) v.push_back({p, C * D * e});
   }
+  if (s->kind == K_HMC && mass_mode == 2) {  // the dense metric: float64 masters, counters, pooled statistics
+    HmcDense& d = s->hd;
+    v.push_back({d.minv, D * D * 8});
+    v.push_back({d.afac, D * D * 8});
+    v.push_back({d.counters, 2 * sizeof(long long)});
+    v.push_back({d.c0, D * 8});
+    v.push_back({d.s1, D * 8});
+    v.push_back({d.S2, D * D * 8});
+  }
   return v;
 }
 size_t parts_bytes(const std::vector<StatePart>& v) {
@@ -1732,7 +2118,7 @@ size_t parts_bytes(const std::vector<StatePart>& v) {
   return b;
 }
 int state_mode(gm_sampler* s) {
-  return s->kind == K_NUTS ? s->nuts.mass_mode : s->kind == K_HMC && s->ha.has ? 1 : 0;
+  return s->kind == K_NUTS ? s->nuts.mass_mode : s->kind == K_HMC && s->ha.has ? (s->hd.on ? 2 : 1) : 0;
 }
 size_t state_bytes(gm_sampler* s) { return parts_bytes(state_parts_for(s, state_mode(s))); }
 }  // namespace
@@ -1817,7 +2203,7 @@ int gm_state_save(gm_sampler* s, void* out, uint64_t bytes) {
   }
   if (s->kind == K_HMC && s->ha.has) {
     const HmcAdapt& a = s->ha;
-    h.mass_mode = 1;
+    h.mass_mode = s->hd.on ? 2 : 1;  // 2: a dense metric follows the per-chain parts
     h.m_sb = a.sb;
     h.m_eb = a.eb;
     h.sched_len = a.iw;
@@ -1852,7 +2238,12 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
   switch (s->kind) {
     case K_HMC:
       GM_REQ(h.eps == s->eps && h.L == s->L, "state blob is for a different step size / n_leapfrog");
-      GM_REQ(h.mass_mode == 0 || h.mass_mode == 1, "corrupt state blob (per-chain state flag)");
+      GM_REQ(h.mass_mode >= 0 && h.mass_mode <= 2, "corrupt state blob (per-chain state flag)");
+      if (h.mass_mode == 2) {
+        const Layout def = default_layout(s->D, s->dt, s->tg.kind);
+        GM_REQ(s->D >= 2 && s->D <= GM_DENSE_MAX_DIM && s->lay.lanes == def.lanes && s->lay.elems == def.elems,
+               "state blob carries a dense metric: not for this dim or layout");
+      }
       if (h.mass_mode) {
         GM_REQ((h.nuts_m & 0xff) <= 2 && (h.nuts_m & ~0x1ffLL) == 0 && h.nuts_n_discard >= 0 &&
                    h.sched_next >= 0 && h.m_sb >= 0 && h.m_eb >= 0 && h.sched_len >= 0,
@@ -1882,9 +2273,11 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
   }
   if (s->kind == K_HMC) {
     if (h.mass_mode) {
-      const int rc = hmc_adapt_ensure(s);
+      const int rc = h.mass_mode == 2 ? hmc_dense_ensure(s) : hmc_adapt_ensure(s);
       if (rc) return rc;
+      if (h.mass_mode != 2) hmc_dense_free(s);
     } else {
+      hmc_dense_free(s);
       hmc_adapt_free(s);  // the blob's sampler ran the plain path
     }
   }
@@ -1914,6 +2307,14 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
     a.armed = (h.nuts_m >> 8) & 1;
     a.k = h.nuts_n_discard;
     a.rn = h.sched_next;
+    if (h.mass_mode == 2) {  // the sampler-dtype copies of the restored masters
+      const size_t DD = (size_t)s->D * s->D;
+      std::vector<double> mi(DD), af(DD);
+      GM_HIP(hipMemcpy(mi.data(), s->hd.minv, DD * 8, hipMemcpyDeviceToHost));
+      GM_HIP(hipMemcpy(af.data(), s->hd.afac, DD * 8, hipMemcpyDeviceToHost));
+      const int rc = hmc_dense_put_copies(s, mi.data(), af.data());
+      if (rc) return rc;
+    }
   }
   return GM_OK;
 }
@@ -2004,6 +2405,7 @@ int gm_destroy(gm_sampler* s) {
   if (s->d_mct) hipFree(s->d_mct);
   nuts_free_state(&s->nuts);
   hmc_adapt_free(s);
+  hmc_dense_free(s);
   if (s->stream) hipStreamDestroy(s->stream);
   delete s;
   return GM_OK;

@@ -86,7 +86,8 @@ typedef struct gm_target {
 
 /* Compile a CUSTOM target's source for the sampler kernels without running it
  * (kind: 1 HMC, 2 MH, 3 NUTS, 4 HMC with per-chain step sizes / metric /
- * warm-up, 0 log-density/gradient); GM_EINVAL with the
+ * warm-up, 5 HMC with a dense metric (2 <= dim <= 64),
+ * 0 log-density/gradient); GM_EINVAL with the
  * compiler log in gm_last_error() when it does not compile. */
 int gm_custom_target_check(const char* source, gm_dtype dtype, int64_t dim, int32_t kind);
 
@@ -179,6 +180,46 @@ int gm_hmc_set_metric(gm_sampler* s, const void* diag_inv);
 /* M^-1 and sqrt(M), [n_chains][dim] of the sampler dtype, either may be NULL;
  * ones before any of these calls. */
 int gm_hmc_get_metric(gm_sampler* s, void* diag_inv, void* diag_sqrt);
+
+/* ---- HMC warm-up: one dense metric shared by all chains ---------------------
+ * Stan's convention: M^-1 = Sigma, the regularised covariance of the warm-up
+ * positions POOLED over all chains of the sampler (they target one
+ * distribution). With Sigma = L L^T and A = L^-T a transition draws p = A z
+ * from the same momentum normals z, drifts with q += eps * Sigma p and weighs
+ * the kinetic energy 0.5 p' Sigma p; with Sigma = I it returns the bits of the
+ * plain path. Step sizes stay per chain (gm_hmc_set_step_sizes /
+ * gm_hmc_get_step_sizes work unchanged). A sampler on which none of these
+ * calls was made runs exactly as before.
+ * Shapes: an HMC sampler (GM_ESTATE otherwise) with 2 <= dim <= 64 at the
+ * dim's default layout, next_pow2(dim) x 1 for a built-in target and 1 x dim
+ * for a CUSTOM one, whose source is compiled into the kernel at the first of
+ * these calls (GM_EINVAL otherwise; a dense-metric sampler refuses
+ * gm_sampler_set_layout to another layout).
+ *
+ * gm_hmc_set_dense_adaptation arms the warm-up (the n_discard transitions of
+ * the next gm_run* call, as gm_hmc_set_adaptation): per-chain dual averaging
+ * of the step size and, in the windows of the same schedule, float64 pooled
+ * statistics of every chain's position. At a window end with >= 5 transitions
+ * collected: Sigma = (1 - regularize) S + regularize I (S the pooled sample
+ * covariance), each diagonal entry floored at max(jitter, 1e-10), factored in
+ * float64; a failed factorisation keeps the previous metric and is counted;
+ * either way the statistics reset and the dual averaging restarts from
+ * eps_bar. It drops any per-chain diagonal metric and keeps the step sizes and
+ * a dense metric already set. Validation as gm_hmc_set_adaptation.
+ * gm_hmc_set_adaptation drops the dense metric (every mode); gm_hmc_set_metric
+ * and gm_hmc_get_metric return GM_ESTATE on a dense-metric sampler. */
+int gm_hmc_set_dense_adaptation(gm_sampler* s, double target_accept, int64_t start_buffer, int64_t end_buffer,
+                                int64_t initial_window, double regularize, double jitter);
+/* M^-1 = minv [dim][dim], float64: finite, exactly symmetric and positive
+ * definite (GM_EINVAL otherwise, the sampler unchanged). On a sampler without
+ * a dense metric it also drops any per-chain diagonal metric and disarms a
+ * warm-up armed by gm_hmc_set_adaptation (the step sizes stay); on a
+ * dense-metric sampler an armed dense warm-up stays armed. */
+int gm_hmc_set_dense_metric(gm_sampler* s, const double* minv);
+/* minv = Sigma and a_factor = A = L^-T (upper triangular), [dim][dim] float64
+ * row-major; the numbers of metric updates and of failed factorisations of the
+ * warm-ups so far. Any pointer may be NULL. GM_ESTATE without a dense metric. */
+int gm_hmc_get_dense_metric(gm_sampler* s, double* minv, double* a_factor, int64_t* updates, int64_t* failed);
 
 /* MetropolisHastings::new (metropolis_hastings.rs:151-161) with an
  * IsotropicGaussian proposal of standard deviation proposal_std
