@@ -96,6 +96,7 @@ SIGNATURES = {
     "gm_get_positions": (_ip, [_vp, _vp]),
     "gm_set_positions": (_ip, [_vp, _vp]),
     "gm_get_accept_counts": (_ip, [_vp, _vp]),
+    "gm_get_logp": (_ip, [_vp, _vp]),
     "gm_get_leapfrog_counts": (_ip, [_vp, _vp]),
     "gm_nuts_get_step_size": (_ip, [_vp, _vp, _vp]),
     "gm_nuts_set_mass_adaptation": (_ip, [_vp, _i32, _i64, _i64, _i64, _dbl, _dbl, _i64]),

@@ -189,6 +189,12 @@ class Sampler:
         _lib.check(self._lib.gm_get_accept_counts(self._h, _lib.ptr(out)))
         return out
 
+    def logp(self) -> np.ndarray:
+        """HMC and MH: each chain's log-density as the last launch computed it."""
+        out = np.empty(self.n_chains, dtype=self.dtype)
+        _lib.check(self._lib.gm_get_logp(self._h, _lib.ptr(out)))
+        return out
+
     def leapfrog_counts(self) -> np.ndarray:
         out = np.empty(self.n_chains, dtype=np.int64)
         _lib.check(self._lib.gm_get_leapfrog_counts(self._h, _lib.ptr(out)))
@@ -226,7 +232,7 @@ class Sampler:
         return self
 
     def set_unroll(self, n: int):
-        """HMC leapfrog-loop unroll: 0 automatic, or 1, 2, 4 (same results)."""
+        """HMC leapfrog-loop form: 0 automatic, or 1, 2, 4, 7 (the long count-down form); same results."""
         _lib.check(self._lib.gm_sampler_set_unroll(self._h, int(n)))
         return self
 

@@ -18,6 +18,11 @@ struct TrackLaunch {
 };
 
 // ---- HMC -------------------------------------------------------------------
+// The long leapfrog loop form of hmc_kernel (hmc_device.h): count-down trips
+// of GM_LF_LONG straight-line leapfrogs. The value is also the form's
+// lf_unroll / gm_sampler_set_unroll number.
+constexpr int GM_LF_LONG = 7;
+
 struct HmcLaunch {
   void* q = nullptr;            // [C*D] state, in/out
   void* logp = nullptr;         // [C] out
@@ -33,7 +38,7 @@ struct HmcLaunch {
   int n_steps = 0;
   int collect_from = 0;         // steps s >= collect_from are stored ...
   long long sample_row0 = 0;    // ... at row sample_row0 + (s - collect_from)
-  int lf_unroll = 1;            // leapfrog loop unroll (1, 2 or 4; same results)
+  int lf_unroll = 1;            // leapfrog loop form (1, 2, 4 or GM_LF_LONG; same results)
   void* zs = nullptr;           // wide layouts: momentum block scratch [C][S][lanes*elems]
 };
 

@@ -254,7 +254,7 @@ struct gm_sampler {
   bool lay_from_wide = false;  // NUTS: a wide layout replaced for a dense metric (gm_nuts_set_mass_adaptation)
   Layout lay_wide{};            // ... and that layout
   long long steps_per_launch = 1000;
-  int lf_unroll = 0;  // HMC leapfrog-loop unroll: 0 by the wave count (hmc_lf_unroll), else 1, 2 or 4
+  int lf_unroll = 0;  // HMC leapfrog-loop form: 0 by the wave count and L (hmc_lf_unroll), else 1, 2, 4 or GM_LF_LONG
   std::vector<hipEvent_t> evs;
   double last_ms = 0;
   long long last_launches = 0;
@@ -924,7 +924,8 @@ int gm_sampler_set_steps_per_launch(gm_sampler* s, int64_t steps) {
 
 int gm_sampler_set_unroll(gm_sampler* s, int32_t n) {
   GM_REQ(s, "sampler is NULL");
-  GM_REQ(n == 0 || n == 1 || n == 2 || n == 4, "unroll must be 0 (automatic), 1, 2 or 4");
+  GM_REQ(n == 0 || n == 1 || n == 2 || n == 4 || n == GM_LF_LONG,
+         "unroll must be 0 (automatic), 1, 2, 4 or 7 (the long count-down form)");
   s->lf_unroll = n;
   return GM_OK;
 }
@@ -954,7 +955,7 @@ int gm_sampler_last_run_stats(gm_sampler* s, double* kernel_ms, int64_t* launche
 // (tools/probe_hmc_scaling.py): x4 is ~12% faster while the grid has at most
 // one wave per SIMD (latency bound), and 10-20% slower from two waves per
 // SIMD up.
-static int hmc_lf_unroll(long long waves) {
+static int hmc_lf_unroll(long long waves, long long L, bool has_long) {
   static const int simds = [] {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -964,7 +965,12 @@ static int hmc_lf_unroll(long long waves) {
   }();
   // x4 at <= 1 wave per SIMD, x2 at <= 4 (the cfg2 headline), x1 above
   // (cfg4's 8 and the north star's 16 waves per SIMD), measured per regime
-  return waves <= simds ? 4 : waves <= 4 * simds ? 2 : 1;
+  const int form = waves <= simds ? 4 : waves <= 4 * simds ? 2 : 1;
+  // The long count-down form (GM_LF_LONG leapfrogs per trip) where x2 ran:
+  // above one and up to four waves per SIMD, in the kernels that compile it
+  // in (has_long), from the L at which its hot trips carry most of the steps.
+  if (form == 2 && has_long && L - 1 >= 2 * GM_LF_LONG) return GM_LF_LONG;
+  return form;
 }
 
 // hipSetDevice only when the calling thread is on another device (the call
@@ -1021,8 +1027,14 @@ static int run_steps(gm_sampler* s, long long total, long long collect_from, int
   const long long n_launch = (total + chunk - 1) / chunk;
   int rc = ensure_run_events(s);
   if (rc) return rc;
+  // (the long form is compiled into the plain kernel's one-chain-per-wave
+  // layouts with at most two elements per lane, hmc_part.inc, and the warm-up
+  // and dense-metric kernels run it as x1; chosen at one element per lane
+  // only: at two, 4096 chains x 128-D, it measured 3.5 % slower than x2,
+  // profiles/r10/ab_hmc_64x2_4096.log)
+  const bool has_long = !s->ha.has && s->lay.lanes == 64 && s->lay.elems == 1;
   const int lf_unroll = s->kind != K_HMC ? 1 : s->lf_unroll ? s->lf_unroll
-                                                             : hmc_lf_unroll((s->C * s->lay.lanes + 63) / 64);
+                                                             : hmc_lf_unroll((s->C * s->lay.lanes + 63) / 64, s->L, has_long);
   if (s->kind == K_HMC && s->ha.has) {
     const long long warm = s->ha.armed && s->ha.mode ? std::min(pending_warm, total) : 0;
     if (s->hd.on) return run_hmc_dense(s, total, collect_from, hook, chunk, lf_unroll, warm);
@@ -1675,6 +1687,18 @@ int gm_get_accept_counts(gm_sampler* s, int64_t* out) {
   GM_HIP(hipSetDevice(s->device));
   GM_HIP(hipStreamSynchronize(s->stream));
   GM_HIP(hipMemcpy(out, s->d_acc, s->C * sizeof(long long), hipMemcpyDeviceToHost));
+  return GM_OK;
+}
+
+int gm_get_logp(gm_sampler* s, void* out) {
+  GM_REQ(s && out, "bad arguments");
+  if (s->kind == K_NUTS || s->step == 0) {
+    set_error("no launch has written the log-densities (HMC and MH, after the first transition)");
+    return GM_ESTATE;
+  }
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  GM_HIP(hipMemcpy(out, s->d_logp, s->C * s->esz, hipMemcpyDeviceToHost));
   return GM_OK;
 }
 

@@ -10,6 +10,10 @@
 
 namespace gm {
 
+#ifndef GM_LF_U
+#define GM_LF_U GM_LF_LONG  // (measurement builds: the long form's trip length)
+#endif
+
 // a compile-time index handed to a generic lambda, and f(IntC<K>) for K < S
 template <int V> struct IntC { static constexpr int v = V; };
 template <int K, int S, class F> __device__ __forceinline__ void for_each_k(F&& f) {
@@ -38,8 +42,9 @@ __device__ __forceinline__ T accept_window(uint64_t seed, uint32_t ucid, uint64_
   return glog_unif(um);
 }
 
-// LF: the leapfrog loop form (1, 2 or 4 leapfrogs per trip) as a constant, or
-// 0 for the launch's a.lf_unroll (all three forms in the code).
+// LF: the leapfrog loop form (1, 2 or 4 leapfrogs per trip, or GM_LF_LONG: the
+// long count-down form) as a constant, or 0 for the launch's a.lf_unroll (the
+// forms 1, 2 and 4 in the code; GM_LF_LONG then runs as 1).
 //
 // One chain per wave (LPC = 64): the per-chain sums of a transition are left
 // in row 3 of the wave (lanes 48..63, group_sum_n_row3) and everything derived
@@ -194,15 +199,27 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
 #pragma unroll
       for (int e = 0; e < E; ++e) p1[e] = gfma(g1[e], half, p1[e]);
     };
-    int l = 0;
-    if (lfu == 4)
-      for (; l + 4 < a.L; l += 4) { lf(); lf(); lf(); lf(); }
-    // two leapfrogs per loop trip at 2-4 waves per SIMD (one taken branch and
-    // loop test per two): kernel -1.4 % at the headline's 4 waves per SIMD,
-    // but cfg4 at 8 waves per SIMD -4.7 % (profiles/r04/ab_hmc_unroll2.log)
-    if (lfu == 2)
-      for (; l + 2 < a.L; l += 2) { lf(); lf(); }
-    for (; l + 1 < a.L; ++l) lf();
+    // The long form: single steps bring L - 1 to a multiple of GM_LF_LONG
+    // (none at L = 50), then count-down trips of GM_LF_LONG straight-line
+    // leapfrogs: one scalar decrement, compare and taken branch per trip and
+    // no remainder test in it (7 taken branches per 49 leapfrogs where the x2
+    // form has 25, and 3 scalar instructions per 7 leapfrogs for 5 per 2).
+    if constexpr (LF == GM_LF_LONG) {
+      const int n1 = a.L - 1;
+      int trips = n1 > 0 ? (int)((unsigned)n1 / (unsigned)GM_LF_U) : 0;
+      for (int r = n1 - trips * GM_LF_U; r > 0; --r) lf();
+      for (; trips > 0; --trips) for_each_k<0, GM_LF_U>([&](auto) __attribute__((always_inline)) { lf(); });
+    } else {
+      int l = 0;
+      if (lfu == 4)
+        for (; l + 4 < a.L; l += 4) { lf(); lf(); lf(); lf(); }
+      // two leapfrogs per loop trip at 2-4 waves per SIMD (one taken branch and
+      // loop test per two): kernel -1.4 % at the headline's 4 waves per SIMD,
+      // but cfg4 at 8 waves per SIMD -4.7 % (profiles/r04/ab_hmc_unroll2.log)
+      if (lfu == 2)
+        for (; l + 2 < a.L; l += 2) { lf(); lf(); }
+      for (; l + 1 < a.L; ++l) lf();
+    }
     // 6. proposed kinetic energy, from the in-lane sums of p'^2
     auto kin_part = [&]() __attribute__((always_inline)) {
       T kq = (T)0;

@@ -19,6 +19,8 @@ hipError_t GM_HMC_NAME(const TargetDev& tg, const Layout& lay, const HmcLaunch& 
     // shapes): the leapfrog loop form is compiled in, so each of the S
     // unrolled block positions carries one form instead of three
     if constexpr (LPC == 64 && E <= 2) {
+      if (a.lf_unroll == GM_LF_LONG)
+        return launch_timed(hmc_kernel<T, LPC, E, TG, GM_LF_LONG>, dim3(blocks), dim3(256), lds, st, ev, a, t);
       if (a.lf_unroll == 4)
         return launch_timed(hmc_kernel<T, LPC, E, TG, 4>, dim3(blocks), dim3(256), lds, st, ev, a, t);
       if (a.lf_unroll == 2)

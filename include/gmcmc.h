@@ -293,6 +293,11 @@ int gm_set_positions(gm_sampler* s, const void* in);
  * (the quantity behind MultiChainTracker::p_accept, stats.rs:238-269). */
 int gm_get_accept_counts(gm_sampler* s, int64_t* out);
 
+/* HMC and MH: the log-density of each chain's current position as the last
+ * launch computed it ([n_chains] of the sampler's dtype). GM_ESTATE before the
+ * first transition and for NUTS. Tests and diagnostics. */
+int gm_get_logp(gm_sampler* s, void* out);
+
 /* Per-chain count of leapfrog steps integrated since creation (HMC:
  * n_leapfrog per transition; NUTS: the tree sizes actually built; MH: 0). */
 int gm_get_leapfrog_counts(gm_sampler* s, int64_t* out);
@@ -385,9 +390,11 @@ int gm_sampler_synchronize(gm_sampler* s);
 /* Transitions per kernel launch (state stays in registers inside a launch). */
 int gm_sampler_set_steps_per_launch(gm_sampler* s, int64_t steps);
 
-/* HMC leapfrog-loop unroll of the fused kernel: 0 (default) chosen by the
- * launch's waves per SIMD, or forced to 1, 2 or 4 (tests and measurements;
- * identical results in every form). No reference counterpart. */
+/* HMC leapfrog-loop form of the fused kernel: 0 (default) chosen by the
+ * launch's waves per SIMD and L, or forced to 1, 2 or 4 leapfrogs per loop
+ * trip or to 7, the long count-down form (7 per trip after (L - 1) % 7 single
+ * ones; the kernels that do not compile it in run it as 1). Tests and
+ * measurements; identical results in every form. No reference counterpart. */
 int gm_sampler_set_unroll(gm_sampler* s, int32_t n);
 
 /* Pre-size the device sample buffer for runs collecting up to n_collect
