@@ -98,6 +98,12 @@ SIGNATURES = {
     "gm_get_accept_counts": (_ip, [_vp, _vp]),
     "gm_get_logp": (_ip, [_vp, _vp]),
     "gm_get_leapfrog_counts": (_ip, [_vp, _vp]),
+    "gm_sampler_set_stats": (_ip, [_vp, _i32]),
+    "gm_sampler_stats_info": (_ip, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32)]),
+    "gm_sampler_stats_device": (_ip, [_vp, C.POINTER(_vp)]),
+    "gm_sampler_stats_field": (_ip, [_vp, _i32, _vp]),
+    "gm_sampler_stats_reduce": (_ip, [_vp, _i64, _i64, _vp, _vp]),
+    "gm_stats_reduce_device": (_ip, [_vp, _ip, _i64, _i64, _i64, _i32, _vp, _vp]),
     "gm_nuts_get_step_size": (_ip, [_vp, _vp, _vp]),
     "gm_nuts_set_mass_adaptation": (_ip, [_vp, _i32, _i64, _i64, _i64, _dbl, _dbl, _i64]),
     "gm_nuts_set_lds_levels": (_ip, [_vp, _i32]),

@@ -7,8 +7,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .stats import (ChainStats, Progress, RunStats, _print_progress, split_rhat_mean_ess_device,
-                    summary_device)
+from .stats import (ChainStats, Progress, RunStats, SamplerStats, _print_progress,
+                    split_rhat_mean_ess_device, summary_device)
 
 
 @dataclass
@@ -56,6 +56,40 @@ class DeviceSamples:
         self.owner.synchronize()
         return summary_device(self.ptr, self.dtype, self.n_chains, self.n_collect, self.dim,
                               (self.dim, self.n_chains * self.dim, 1), probs)
+
+    @property
+    def stats(self) -> SamplerStats:
+        """The run's per-transition sampler statistics (Sampler.collect_stats)."""
+        self._check_live()
+        return SamplerStats(self.owner)
+
+    def logp(self) -> np.ndarray:
+        """The target's log-density of every stored draw, [n_chains, n_collect]
+        on the host, evaluated where the draws lie (batch_vector.BatchTarget)."""
+        from .batch_vector import BatchTarget, DeviceMatrix
+        self._check_live()
+        self.owner.synchronize()
+        out = np.empty((self.n_collect, self.n_chains), dtype=self.dtype)
+        if self.n_collect == 0:
+            return out.T.copy()
+        tg = BatchTarget(self.owner.target(), self.dim, self.dtype)
+        item = np.dtype(self.dtype).itemsize
+        # rows per evaluation: the gradient scratch stays within 64 MiB
+        step = max(1, min(self.n_collect, (64 << 20) // (self.n_chains * self.dim * item)))
+        grad = DeviceMatrix((step * self.n_chains, self.dim), self.dtype)
+        lp = DeviceMatrix((step * self.n_chains,), self.dtype)
+        try:
+            for r0 in range(0, self.n_collect, step):
+                n = min(step, self.n_collect - r0)
+                x = C.c_void_p(self.ptr + r0 * self.n_chains * self.dim * item)
+                _lib.check(tg.lib.gm_bv_logp_and_grad(tg.h, n * self.n_chains, x, C.c_void_p(grad.ptr),
+                                                      C.c_void_p(lp.ptr)))
+                out[r0:r0 + n] = lp.to_host()[:n * self.n_chains].reshape(n, self.n_chains)
+        finally:
+            grad.close()
+            lp.close()
+            tg.close()
+        return np.ascontiguousarray(out.T)
 
 
 class Sampler:
@@ -226,6 +260,22 @@ class Sampler:
 
     def synchronize(self):
         _lib.check(self._lib.gm_sampler_synchronize(self._h))
+
+    def collect_stats(self, mode=True):
+        """HMC / NUTS: record per-transition sampler statistics (energy,
+        accept_stat, step_size, n_leapfrog, tree_depth, divergent, accepted)
+        in the following runs: True or "collected" for the transitions behind
+        the collected rows, "all" for the warm-up as well, False for none.
+        Samples are bit for bit those of a run without (gm_sampler_set_stats)."""
+        codes = {False: 0, None: 0, "off": 0, True: 1, "collected": 1, "all": 2}
+        if mode not in codes:
+            raise ValueError('mode must be True, "collected", "all" or False')
+        _lib.check(self._lib.gm_sampler_set_stats(self._h, codes[mode]))
+        return self
+
+    def last_stats(self) -> SamplerStats:
+        """The sampler statistics of the last run (after collect_stats)."""
+        return SamplerStats(self)
 
     def set_steps_per_launch(self, n: int):
         _lib.check(self._lib.gm_sampler_set_steps_per_launch(self._h, n))

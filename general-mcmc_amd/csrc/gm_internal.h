@@ -114,6 +114,16 @@ hipError_t launch_mct_step(gm_dtype dt, long long C, int P, const void* x, float
 hipError_t launch_mct_rhat(long long C, int P, unsigned long long n, const float* mean, const float* msq,
                            float* rhat, hipStream_t st);
 
+// ---- per-transition sampler statistics (stats_kernels.hip) -------------------
+// The reduction of record rows [r0, r0 + rows) of rec [.][C] (StatsRec of the
+// dtype): out [GM_STATS_FIELDS][C] and the chains' totals tot
+// [GM_STATS_FIELDS] (include/gmcmc.h), float64 on the device; scratch:
+// stats_reduce_scratch_bytes(C, rows) bytes. max_depth 0: nothing counts as
+// having reached it (HMC).
+size_t stats_reduce_scratch_bytes(long long C, long long rows);
+hipError_t launch_stats_reduce(gm_dtype dt, const void* rec, long long C, long long r0, long long rows,
+                               int max_depth, double* scratch, double* out, double* tot, hipStream_t st);
+
 // ---- MH --------------------------------------------------------------------
 hipError_t launch_mh(gm_dtype dt, const TargetDev& tg, const Layout& lay, const MhLaunch& a,
                      hipStream_t st, LaunchEvents ev = {});

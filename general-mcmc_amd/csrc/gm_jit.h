@@ -32,7 +32,9 @@ enum JitKernel {
   JIT_HMC_ADAPT2 = 6,
   // hmc_dense_kernel (hmc_dense_device.h), MODE 0, 1
   JIT_HMC_DENSE0 = 7,
-  JIT_HMC_DENSE1 = 8
+  JIT_HMC_DENSE1 = 8,
+  // nuts_kernel with the per-transition records (REC)
+  JIT_NUTS_REC = 9
 };
 
 // Host mirror of the device adapter gm::UserTarget<T> (kernel argument).

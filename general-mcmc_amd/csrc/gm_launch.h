@@ -17,6 +17,52 @@ struct TrackLaunch {
   unsigned long long n0 = 0;
 };
 
+// ---- per-transition sampler statistics (gm_sampler_set_stats) ---------------
+// One record per (transition, chain), [n_transitions][n_chains], written by
+// the chain's lane 0 as one aligned store: three values of the sampler dtype
+// and a count word, 16 bytes (f32) or 32 (f64; the word's upper half is zero).
+// The word, the same for both dtypes:
+//   bits 0-23 n_leapfrog (saturating), 24-29 tree_depth, 30 divergent, 31 accepted
+template <class T> struct StatsWord;
+template <> struct StatsWord<float> { typedef uint32_t type; };
+template <> struct StatsWord<double> { typedef uint64_t type; };
+template <class T> struct alignas(4 * sizeof(T)) StatsRec {
+  T energy;       // the Hamiltonian after the momentum refresh: K(p0) - logp(q)
+  T accept_stat;  // NUTS alpha / n_alpha; HMC min(1, exp(log_alpha)), NaN -> 0
+  T step_size;    // the step size the transition integrated with
+  typename StatsWord<T>::type word;
+};
+constexpr uint32_t GM_STATS_NLF_MAX = (1u << 24) - 1;
+__host__ __device__ constexpr uint32_t stats_word(long long n_leapfrog, int tree_depth, bool divergent,
+                                                  bool accepted) {
+  return (n_leapfrog > (long long)GM_STATS_NLF_MAX ? GM_STATS_NLF_MAX : (uint32_t)n_leapfrog) |
+         ((uint32_t)(tree_depth & 63) << 24) | (divergent ? 1u << 30 : 0u) | (accepted ? 1u << 31 : 0u);
+}
+// rec is null when statistics are off. Transition s of a launch (0-based) has
+// the run index t0 + s and goes to record row t0 + s - first when that is in
+// [0, n): `first` is the run's first recorded transition.
+struct StatsLaunch {
+  void* rec = nullptr;
+  long long t0 = 0;
+  long long first = 0;
+  long long n = 0;
+};
+// the record of chain c (of C) for transition s of the launch; called by one
+// lane of the chain, with st.rec non-null
+template <class T>
+__device__ __forceinline__ void stats_store(const StatsLaunch& st, long long C, long long c, long long s, T energy,
+                                            T accept_stat, T step_size, uint32_t word) {
+  const long long r = st.t0 + s - st.first;
+  if (r >= 0 && r < st.n) {
+    StatsRec<T> v;
+    v.energy = energy;
+    v.accept_stat = accept_stat;
+    v.step_size = step_size;
+    v.word = word;
+    ((StatsRec<T>*)st.rec)[r * C + c] = v;
+  }
+}
+
 // ---- HMC -------------------------------------------------------------------
 // The long leapfrog loop form of hmc_kernel (hmc_device.h): count-down trips
 // of GM_LF_LONG straight-line leapfrogs. The value is also the form's
@@ -61,6 +107,7 @@ struct HmcAdaptLaunch {
   long long rn0 = 0;            // Welford count before this launch
   long long m0 = 0;             // warm-up transitions before this launch (m = m0 + s + 1)
   long long sb = 0, lim = 0;    // Welford collects while sb < m < lim (lim = n_discard - end_buffer)
+  StatsLaunch stats;            // per-transition records (off when stats.rec is null)
 };
 
 // ---- HMC with per-chain step sizes and one dense metric for all chains --------
@@ -77,6 +124,7 @@ struct HmcDenseLaunch {
   const void* at = nullptr;     // [D][D] at[j*D + i] = A_ij, A = L^-T upper triangular (zeros below)
   double delta = 0.8;           // target acceptance
   long long k0 = 0;             // dual-averaging restart counter before this launch
+  StatsLaunch stats;            // per-transition records (off when stats.rec is null)
 };
 // hmc_dense_kernel's workgroup stays within 64 KiB of LDS: its static part
 // (the f32 Box-Muller tables, 3 KiB; the f64 kernels do not use them and the
@@ -202,6 +250,15 @@ struct NutsLaunch {
   // applies L and M^-1 to zmom's normals itself.
   const void* pv0 = nullptr;
 };
+// The argument block of the recording instantiations (nuts_kernel REC): the
+// same block with the records' after it. The others keep NutsLaunch as it
+// is: 32 more bytes of kernel arguments changed the frozen-dense kernel's
+// register allocation (cfg3_dense about 1 % slower with statistics off).
+struct NutsRecLaunch : NutsLaunch {
+  StatsLaunch stats;
+};
+template <bool REC> struct NutsLaunchOf { typedef NutsLaunch type; };
+template <> struct NutsLaunchOf<true> { typedef NutsRecLaunch type; };
 // the frozen-dense kernel takes its momenta from the pass (pv0 always set;
 // nuts_run launches it for no other launch). 0: A/B builds only, the kernel
 // applies the metric itself when pv0 is null

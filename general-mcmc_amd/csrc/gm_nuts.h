@@ -68,7 +68,8 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
              uint64_t seed, uint64_t* step, uint32_t chain_offset, long long total,
              long long n_discard, int progress, long long steps_per_launch, hipStream_t st,
              std::vector<hipEvent_t>& evs, double* ms, long long* launches,
-             const TrackLaunch* trk = nullptr, const StepHook* hook = nullptr);
+             const TrackLaunch* trk = nullptr, const StepHook* hook = nullptr,
+             const StatsLaunch* stats = nullptr);  // stats: the run's records; t0 the run index of this call's first transition
 int nuts_set_mass(NutsState* ns, gm_dtype dt, long long C, int D, int mode, long long start_buffer,
                   long long end_buffer, long long initial_window, double regularize, double jitter);
 int nuts_get_mass(NutsState& ns, gm_dtype dt, long long C, int D, int32_t* kind, void* dinv, void* dsqrt,

@@ -220,6 +220,25 @@ struct HmcDense {
 // the slab's bound (GM_DENSE_MAX_DIM: gm_internal.h)
 constexpr size_t GM_DENSE_SLAB_BYTES = 64u << 20;
 
+// Per-transition sampler statistics (gm_sampler_set_stats; gm_launch.h
+// StatsRec). A run option: nothing of it enters a checkpoint.
+struct StatsRun {
+  int mode = 0;         // 0 off, 1 collected, 2 all
+  void* buf = nullptr;  // the last recording run's records [n][C]
+  size_t cap = 0;
+  bool active = false;  // a gm_run* call is recording (gm_step never does)
+  bool valid = false;   // the last run recorded: buf, n, first_collected and first_row are its
+  long long base = 0;   // run index of the first transition of the next run_steps call
+  long long first = 0;  // the run's first recorded transition
+  long long n = 0;      // transitions recorded
+  long long first_collected = 0, first_row = 0;
+  // a plain HMC sampler's recording launches: per-chain state of the creation
+  // step size and the identity metric for hmc_adapt_kernel's frozen mode
+  HmcAdapt ident;
+  void* scratch = nullptr;  // the reduction's scratch and outputs
+  size_t scratch_cap = 0;
+};
+
 struct gm_sampler {
   int kind = 0;
   gm_dtype dt = GM_F32;
@@ -266,6 +285,7 @@ struct gm_sampler {
   NutsState nuts;
   HmcAdapt ha;
   HmcDense hd;
+  StatsRun st;
   // run_progress statistics: per-chain trackers (MH, NUTS) and a
   // MultiChainTracker (HMC), one allocation each (TrackSet)
   void* d_trk = nullptr;
@@ -367,14 +387,14 @@ static int get_as(gm_dtype dt, const void* src, size_t n, double* dst) {
 }
 
 // ---- HMC per-chain step sizes / metric state (HmcAdapt) --------------------
-static void hmc_adapt_free(gm_sampler* s) {
-  HmcAdapt& h = s->ha;
+static void hmc_adapt_free(HmcAdapt& h) {
   for (void** p : {&h.eps, &h.eps_bar, &h.h_bar, &h.mu, &h.dinv, &h.dsq, &h.rmean, &h.rm2}) {
     if (*p) hipFree(*p);
     *p = nullptr;
   }
   h = HmcAdapt();
 }
+static void hmc_adapt_free(gm_sampler* s) { hmc_adapt_free(s->ha); }
 
 // the step size the kernels use for a chain without per-chain state
 static double hmc_eps_rounded(const gm_sampler* s) { return s->dt == GM_F32 ? (double)(float)s->eps : s->eps; }
@@ -382,8 +402,7 @@ static double hmc_eps_rounded(const gm_sampler* s) { return s->dt == GM_F32 ? (d
 // Allocates the per-chain arrays in their start state: every step size the
 // creation value, the identity metric, no statistics. From here on the sampler
 // runs hmc_adapt_kernel.
-static int hmc_adapt_ensure(gm_sampler* s) {
-  HmcAdapt& h = s->ha;
+static int hmc_adapt_ensure(gm_sampler* s, HmcAdapt& h) {
   if (h.has) return GM_OK;
   if (s->tg.kind == GM_TARGET_CUSTOM) {  // a source that does not compile for this kernel fails here
     const int rc = jit_prepare(JIT_HMC_ADAPT0, s->dt, s->tg);
@@ -396,7 +415,7 @@ static int hmc_adapt_ensure(gm_sampler* s) {
   for (void** p : {&h.dinv, &h.dsq, &h.rmean, &h.rm2})
     if (e == hipSuccess) e = hipMalloc(p, CD * s->esz);
   if (e != hipSuccess) {
-    hmc_adapt_free(s);
+    hmc_adapt_free(h);
     set_error(std::string("per-chain HMC state allocation failed: ") + hipGetErrorString(e));
     return GM_ENOMEM;
   }
@@ -418,13 +437,14 @@ static int hmc_adapt_ensure(gm_sampler* s) {
   }
   if (rc) {
     const std::string msg = gm_last_error();
-    hmc_adapt_free(s);
+    hmc_adapt_free(h);
     set_error(msg);
     return rc;
   }
   h.has = true;
   return GM_OK;
 }
+static int hmc_adapt_ensure(gm_sampler* s) { return hmc_adapt_ensure(s, s->ha); }
 
 // The gm_hmc_set_* / gm_hmc_get_* calls need an HMC sampler (GM_ESTATE) on a
 // lane-group layout (GM_EINVAL on the wide path of dim > 1024).
@@ -891,6 +911,7 @@ int gm_sampler_set_layout(gm_sampler* s, int32_t lanes, int32_t elems) {
     GM_REQ(!wide || s->kind == K_HMC, "wide layouts (lanes > 64) are for the HMC and NUTS samplers");
   }
   GM_REQ(!(wide && s->ha.has), "per-chain step sizes / metric (gm_hmc_set_*) do not take wide layouts");
+  GM_REQ(!(wide && s->kind == K_HMC && s->st.mode), "sampler statistics (gm_sampler_set_stats) do not take wide HMC layouts");
   GM_REQ((long long)lanes * elems >= s->D, "lanes*elems must cover dim");
   GM_REQ((long long)lanes * elems < 2LL * s->D || lanes == 1 ||
              ((long long)(lanes / 2) * elems < s->D),
@@ -996,6 +1017,48 @@ static int ensure_run_events(gm_sampler* s) {
   return GM_OK;
 }
 
+// ---- per-transition sampler statistics (StatsRun) ---------------------------
+// The start of a recording run of `total` transitions, before anything is
+// launched: the record buffer (an allocation failure is a clean error) and,
+// for a plain HMC sampler, the identity per-chain state. fc: the first
+// transition whose resulting state is a collected row, first_row: that row.
+static int stats_begin(gm_sampler* s, long long total, long long fc, long long first_row) {
+  StatsRun& t = s->st;
+  t.active = false;
+  t.valid = false;
+  if (t.mode == 0) return GM_OK;
+  if (fc > total) fc = total;
+  const long long first = t.mode == 2 ? 0 : fc;
+  const long long n = total - first;
+  int rc = ensure_buf(&t.buf, &t.cap, (size_t)n * (size_t)s->C * 4 * s->esz);
+  if (!rc && s->kind == K_HMC && !s->ha.has) rc = hmc_adapt_ensure(s, t.ident);
+  if (rc) return rc;
+  t.base = 0;
+  t.first = first;
+  t.n = n;
+  t.first_collected = fc - first;
+  t.first_row = first_row;
+  t.valid = true;
+  t.active = n > 0;
+  return GM_OK;
+}
+// ends the recording when the run's entry point returns
+struct StatsScope {
+  gm_sampler* s;
+  ~StatsScope() { s->st.active = false; }
+};
+// the launch block of a launch whose first transition is `pos` of the current run_steps call
+static StatsLaunch stats_launch(const gm_sampler* s, long long pos) {
+  StatsLaunch t;
+  if (s->st.active) {
+    t.rec = s->st.buf;
+    t.t0 = s->st.base + pos;
+    t.first = s->st.first;
+    t.n = s->st.n;
+  }
+  return t;
+}
+
 // Runs `total` transitions; transitions with index >= collect_from (0-based
 // within this call) are stored at sample rows (index - collect_from).
 static int run_hmc_adapt(gm_sampler* s, long long total, long long collect_from, const StepHook* hook,
@@ -1017,10 +1080,11 @@ static int run_steps(gm_sampler* s, long long total, long long collect_from, int
   // NUTS always launches: init_chain_state + row 0 even with zero transitions
   if (total <= 0 && s->kind != K_NUTS) return GM_OK;
   if (s->kind == K_NUTS) {
+    const StatsLaunch sl = stats_launch(s, 0);
     int rc = nuts_run(s->nuts, s->dt, s->tg, s->lay, s->d_q, s->d_acc, s->d_samples, s->C, s->D,
                       s->target_accept, s->seed, &s->step, s->chain_offset, total, collect_from,
                       progress, chunk_override > 0 ? chunk_override : s->steps_per_launch,
-                      s->stream, s->evs, &s->last_ms, &s->last_launches, trk, hook);
+                      s->stream, s->evs, &s->last_ms, &s->last_launches, trk, hook, sl.rec ? &sl : nullptr);
     return rc;
   }
   const long long chunk = chunk_override > 0 ? chunk_override : s->steps_per_launch;
@@ -1032,10 +1096,13 @@ static int run_steps(gm_sampler* s, long long total, long long collect_from, int
   // and dense-metric kernels run it as x1; chosen at one element per lane
   // only: at two, 4096 chains x 128-D, it measured 3.5 % slower than x2,
   // profiles/r10/ab_hmc_64x2_4096.log)
-  const bool has_long = !s->ha.has && s->lay.lanes == 64 && s->lay.elems == 1;
+  // (a recording run of a plain sampler goes through hmc_adapt_kernel's
+  // frozen mode with the identity state of StatsRun: the same bits)
+  const bool adapt_path = s->ha.has || s->st.active;
+  const bool has_long = !adapt_path && s->lay.lanes == 64 && s->lay.elems == 1;
   const int lf_unroll = s->kind != K_HMC ? 1 : s->lf_unroll ? s->lf_unroll
                                                              : hmc_lf_unroll((s->C * s->lay.lanes + 63) / 64, s->L, has_long);
-  if (s->kind == K_HMC && s->ha.has) {
+  if (s->kind == K_HMC && adapt_path) {
     const long long warm = s->ha.armed && s->ha.mode ? std::min(pending_warm, total) : 0;
     if (s->hd.on) return run_hmc_dense(s, total, collect_from, hook, chunk, lf_unroll, warm);
     return run_hmc_adapt(s, total, collect_from, hook, chunk, lf_unroll, warm);
@@ -1139,7 +1206,7 @@ static std::vector<long long> hmc_window_ends(const HmcAdapt& h, long long warm,
 // waits for the device, so asynchronous runs stay asynchronous.
 static int run_hmc_adapt(gm_sampler* s, long long total, long long collect_from, const StepHook* hook,
                          long long chunk, int lf_unroll, long long warm) {
-  HmcAdapt& h = s->ha;
+  HmcAdapt& h = s->ha.has ? s->ha : s->st.ident;
   const long long lim = warm > h.eb ? warm - h.eb : 0;
   std::vector<long long> wends;
   if (h.mode == 2) wends = hmc_window_ends(h, warm, lim);
@@ -1195,6 +1262,7 @@ static int run_hmc_adapt(gm_sampler* s, long long total, long long collect_from,
     a.m0 = pos;
     a.sb = h.sb;
     a.lim = lim;
+    a.stats = stats_launch(s, pos);
     hipError_t e = launch_hmc_adapt(s->dt, s->tg, s->lay, a, in_warm ? h.mode : 0, s->stream, ev);
     if (e == hipSuccess && in_warm) {
       h.k += n;
@@ -1316,6 +1384,7 @@ static int run_hmc_dense(gm_sampler* s, long long total, long long collect_from,
     a.at = d.at_t;
     a.delta = h.delta;
     a.k0 = h.k;
+    a.stats = stats_launch(s, pos);
     // the run's stop event goes after the statistics when this launch has some
     LaunchEvents kev = ev;
     if (in_warm) kev.stop = nullptr;
@@ -1372,13 +1441,20 @@ static int run_impl(gm_sampler* s, int64_t n_collect, int64_t n_discard, int pro
   if (rc) return rc;
   long long total = n_discard + n_collect;
   s->ha.pending_warm = n_discard;
+  s->st.valid = false;
+  StatsScope scope{s};
   if (s->kind == K_NUTS && !progress) {
     // NUTS::run performs n_collect + n_discard - 1 transitions (nuts.rs:232-257);
     // row r is the state after n_discard + r of them.
     if (n_collect == 0) return GM_OK;
     total = n_discard + n_collect - 1;
+    // (transition t ends in row t + 1 - n_discard; row 0 of a run without burn-in is the start state)
+    rc = stats_begin(s, total, n_discard > 0 ? n_discard - 1 : 0, n_discard > 0 ? 0 : 1);
+    if (rc) return rc;
     return run_steps(s, total, n_discard, progress ? 1 : 0);
   }
+  rc = stats_begin(s, total, n_discard, 0);
+  if (rc) return rc;
   return run_steps(s, total, n_discard, progress ? 1 : 0);
 }
 
@@ -1527,6 +1603,9 @@ int gm_run_progress_cb(gm_sampler* s, int64_t n_collect, int64_t n_discard, void
   if (rc) return rc;
   const long long C = s->C, total = n_collect + n_discard;
   const int D = s->D;
+  StatsScope scope{s};
+  rc = stats_begin(s, total, n_discard, 0);
+  if (rc) return rc;
   using clk = std::chrono::steady_clock;
   auto t_last = clk::now();
   auto due = [&](bool last) {
@@ -1548,6 +1627,7 @@ int gm_run_progress_cb(gm_sampler* s, int64_t n_collect, int64_t n_discard, void
       rc = run_steps(s, n_discard, n_discard, 1);
       if (rc) return rc;
     }
+    s->st.base = n_discard;  // the collection's records go on from the burn-in's
     StepHook hook;
     unsigned long long mct_n = 0;
     if (cb) {
@@ -1709,6 +1789,137 @@ int gm_get_leapfrog_counts(gm_sampler* s, int64_t* out) {
   if (s->kind == K_NUTS) return nuts_get_leapfrogs(s->nuts, s->C, (long long*)out);
   for (long long i = 0; i < s->C; ++i) out[i] = s->kind == K_HMC ? (int64_t)s->total_steps * s->L : 0;
   return GM_OK;
+}
+
+// ---- per-transition sampler statistics --------------------------------------
+int gm_sampler_set_stats(gm_sampler* s, int32_t mode) {
+  GM_REQ(s, "sampler is NULL");
+  if (s->kind == K_MH) {
+    set_error("sampler statistics are recorded by HMC and NUTS samplers");
+    return GM_ESTATE;
+  }
+  GM_REQ(mode >= 0 && mode <= 2, "mode must be 0 (off), 1 (collected) or 2 (all)");
+  if (s->kind == K_HMC) {
+    GM_REQ(s->D <= 1024 && !layout_is_wide(s->lay), "sampler statistics do not take wide HMC layouts (dim > 1024)");
+    if (mode && !s->ha.has && s->tg.kind == GM_TARGET_CUSTOM) {  // the recording kernel of a plain sampler
+      const int rc = jit_prepare(JIT_HMC_ADAPT0, s->dt, s->tg);
+      if (rc) return rc;
+    }
+  } else if (mode && s->tg.kind == GM_TARGET_CUSTOM) {  // a source that does not compile fails here, not in a run
+    const int rc = jit_prepare(JIT_NUTS_REC, s->dt, s->tg);
+    if (rc) return rc;
+  }
+  s->st.mode = mode;
+  return GM_OK;
+}
+
+// the last run's records, after the run itself
+static int stats_ready(gm_sampler* s) {
+  GM_REQ(s, "sampler is NULL");
+  if (!s->st.valid) {
+    set_error("the last run recorded no statistics (gm_sampler_set_stats, then gm_run*)");
+    return GM_ESTATE;
+  }
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  return GM_OK;
+}
+
+int gm_sampler_stats_info(gm_sampler* s, int64_t* n_transitions, int64_t* first_collected, int64_t* first_row,
+                          int32_t* record_bytes) {
+  const int rc = stats_ready(s);
+  if (rc) return rc;
+  if (n_transitions) *n_transitions = s->st.n;
+  if (first_collected) *first_collected = s->st.first_collected;
+  if (first_row) *first_row = s->st.first_row;
+  if (record_bytes) *record_bytes = (int32_t)(4 * s->esz);
+  return GM_OK;
+}
+
+int gm_sampler_stats_device(gm_sampler* s, const void** records) {
+  const int rc = stats_ready(s);
+  if (rc) return rc;
+  GM_REQ(records, "records is NULL");
+  *records = s->st.n > 0 ? s->st.buf : nullptr;
+  return GM_OK;
+}
+
+extern "C++" {
+template <class T>
+static void stats_unpack(const std::vector<unsigned char>& raw, long long n, long long C, int field, void* out) {
+  const StatsRec<T>* r = (const StatsRec<T>*)raw.data();
+  for (long long t = 0; t < n; ++t)
+    for (long long c = 0; c < C; ++c) {
+      const StatsRec<T>& v = r[t * C + c];
+      const uint32_t w = (uint32_t)v.word;
+      const long long o = c * n + t;
+      switch (field) {
+        case GM_STAT_ENERGY: ((T*)out)[o] = v.energy; break;
+        case GM_STAT_ACCEPT_STAT: ((T*)out)[o] = v.accept_stat; break;
+        case GM_STAT_STEP_SIZE: ((T*)out)[o] = v.step_size; break;
+        case GM_STAT_N_LEAPFROG: ((int32_t*)out)[o] = (int32_t)(w & GM_STATS_NLF_MAX); break;
+        case GM_STAT_TREE_DEPTH: ((int32_t*)out)[o] = (int32_t)((w >> 24) & 63u); break;
+        case GM_STAT_DIVERGENT: ((uint8_t*)out)[o] = (uint8_t)((w >> 30) & 1u); break;
+        default: ((uint8_t*)out)[o] = (uint8_t)((w >> 31) & 1u); break;
+      }
+    }
+}
+}  // extern "C++"
+
+int gm_sampler_stats_field(gm_sampler* s, int32_t field, void* out) {
+  const int rc = stats_ready(s);
+  if (rc) return rc;
+  GM_REQ(field >= GM_STAT_ENERGY && field <= GM_STAT_ACCEPTED, "unknown statistics field");
+  if (s->st.n == 0) return GM_OK;
+  GM_REQ(out, "out is NULL");
+  const size_t bytes = (size_t)s->st.n * (size_t)s->C * 4 * s->esz;
+  std::vector<unsigned char> raw(bytes);
+  GM_HIP(hipMemcpy(raw.data(), s->st.buf, bytes, hipMemcpyDeviceToHost));
+  if (s->dt == GM_F32) stats_unpack<float>(raw, s->st.n, s->C, field, out);
+  else stats_unpack<double>(raw, s->st.n, s->C, field, out);
+  return GM_OK;
+}
+
+// the reduction of rows [row0, row0 + n_rows) of rec on `st`; scratch grows as needed
+static int stats_reduce_impl(const void* rec, gm_dtype dt, long long C, long long row0, long long n_rows,
+                             int max_depth, void** scratch, size_t* cap, hipStream_t st, double* per_chain,
+                             double* total) {
+  const size_t sb = stats_reduce_scratch_bytes(C, n_rows), ob = sizeof(double) * GM_STATS_FIELDS * (size_t)(C + 1);
+  int rc = ensure_buf(scratch, cap, sb + ob);
+  if (rc) return rc;
+  double* out = (double*)((char*)*scratch + sb);
+  double* tot = out + (size_t)GM_STATS_FIELDS * C;
+  hipError_t e = launch_stats_reduce(dt, rec, C, row0, n_rows, max_depth, (double*)*scratch, out, tot, st);
+  if (e != hipSuccess) {
+    set_error(std::string("statistics reduction failed: ") + hipGetErrorString(e));
+    return GM_EHIP;
+  }
+  if (per_chain)
+    GM_HIP(hipMemcpyAsync(per_chain, out, sizeof(double) * GM_STATS_FIELDS * (size_t)C, hipMemcpyDeviceToHost, st));
+  if (total) GM_HIP(hipMemcpyAsync(total, tot, sizeof(double) * GM_STATS_FIELDS, hipMemcpyDeviceToHost, st));
+  GM_HIP(hipStreamSynchronize(st));
+  return GM_OK;
+}
+
+int gm_sampler_stats_reduce(gm_sampler* s, int64_t row0, int64_t n_rows, double* per_chain, double* total) {
+  int rc = stats_ready(s);
+  if (rc) return rc;
+  GM_REQ(row0 >= 0 && n_rows >= 1 && row0 + n_rows <= s->st.n, "rows out of range of the last run's records");
+  return stats_reduce_impl(s->st.buf, s->dt, s->C, row0, n_rows, s->kind == K_NUTS ? s->max_depth : 0,
+                           &s->st.scratch, &s->st.scratch_cap, s->stream, per_chain, total);
+}
+
+int gm_stats_reduce_device(const void* records, gm_dtype dtype, int64_t n_chains, int64_t row0, int64_t n_rows,
+                           int32_t max_depth, double* per_chain, double* total) {
+  GM_REQ(records, "records is NULL");
+  GM_REQ(dtype == GM_F32 || dtype == GM_F64, "dtype must be GM_F32 or GM_F64");
+  GM_REQ(n_chains >= 1 && row0 >= 0 && n_rows >= 1 && max_depth >= 0, "bad shape");
+  void* scratch = nullptr;
+  size_t cap = 0;
+  const int rc = stats_reduce_impl(records, dtype, n_chains, row0, n_rows, max_depth, &scratch, &cap, nullptr,
+                                   per_chain, total);
+  if (scratch) hipFree(scratch);
+  return rc;
 }
 
 int gm_hmc_set_adaptation(gm_sampler* s, int32_t mode, double target_accept, int64_t start_buffer,
@@ -2430,6 +2641,9 @@ int gm_destroy(gm_sampler* s) {
   nuts_free_state(&s->nuts);
   hmc_adapt_free(s);
   hmc_dense_free(s);
+  hmc_adapt_free(s->st.ident);
+  if (s->st.buf) hipFree(s->st.buf);
+  if (s->st.scratch) hipFree(s->st.scratch);
   if (s->stream) hipStreamDestroy(s->stream);
   delete s;
   return GM_OK;

@@ -297,6 +297,14 @@ __global__ __launch_bounds__(256) void hmc_dense_kernel(HmcDenseLaunch aa, TG tg
     }
     // 7-9. Metropolis accept (NaN log_alpha rejects)
     const T log_alpha = (lp1 - lp) + (ke0 - ke1);
+    // the transition's record (gm_launch.h StatsRec), before lp and eps move on
+    if (aa.stats.rec != nullptr && lane == 0) {
+      T al = gexp(log_alpha);
+      al = al > (T)1 ? (T)1 : al;
+      al = (al == al) ? al : (T)0;
+      stats_store<T>(aa.stats, a.C, c, s, ke0 - lp, al, eps,
+                     stats_word(a.L, 0, !(log_alpha > (T)-1000), log_alpha >= lnu));
+    }
     if (log_alpha >= lnu) {
 #pragma unroll
       for (int e = 0; e < E; ++e) {

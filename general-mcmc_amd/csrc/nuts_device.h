@@ -662,12 +662,17 @@ __device__ unsigned long long gm_nuts_prof_buf[NPROF_WAVES * NPROF_SLOTS];
 // fits the registers without spills (64 x 8 / 64 x 16 f64 spilled 77-1268
 // registers, profiles/r04/nuts_resources.txt); nuts_wide_waves (gm_launch.h)
 // waves per SIMD for them.
-template <class T, int LPC, int E, class TG, int MASS>
+// REC: the instantiations that write the per-transition records (gm_launch.h
+// StatsRec; a.stats.rec non-null). They are kernels of their own
+// (nuts_rec_part*.hip, nuts_wide_rec.hip) with an argument block of their own
+// (NutsRecLaunch): a run-time test of the pointer cost the others 2-5 VGPRs,
+// and the frozen-dense one 16 bytes of scratch.
+template <class T, int LPC, int E, class TG, int MASS, bool REC = false>
 __global__ __launch_bounds__(LPC > 256 ? LPC : 256,
                              MASS == 2 ? GM_DENSE_WAVES : MASS == 3 ? GM_FROZEN_WAVES
                              : LPC > 64 ? nuts_wide_waves((int)sizeof(T), E)
                              : (E * (int)sizeof(T) > 32 || (sizeof(T) == 8 && E > 2)) ? 1 : 2)
-void nuts_kernel(NutsLaunch a, TG tg_) {
+void nuts_kernel(typename NutsLaunchOf<REC>::type a, TG tg_) {
   const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long c = gtid / LPC;
   const int lane = (int)(gtid % LPC);
@@ -1017,6 +1022,7 @@ void nuts_kernel(NutsLaunch a, TG tg_) {
   int tn = 0, tna = 0;
   bool ts = true;
   T ta = (T)0;
+  bool moved = false;  // REC: the transition has moved the chain (its record's `accepted`)
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     qe[e] = pe[e] = ge[e] = qf[e] = pf[e] = gf[e] = fq[e] = fp[e] = pr[e] = p0o[e] = (T)0;
@@ -1263,6 +1269,7 @@ void nuts_kernel(NutsLaunch a, TG tg_) {
       j = 0;
       l = 0;
       merge_ctr = 0;
+      if constexpr (REC) moved = false;
       v = (srec ? (dirb & 1u) != 0 : nuts_u<T>(key, 0u) < (T)0.5) ? 1 : -1;  // doubling 0's direction (:783-784)
       starting = false;
       continue;
@@ -1279,6 +1286,9 @@ void nuts_kernel(NutsLaunch a, TG tg_) {
     const T joint = lp - kin;
     tn = (logu < joint) ? 1 : 0;
     ts = (logu - (T)1000) < joint;
+    // a divergent leaf ends its transition in this iteration: ts stays false up
+    // the climb and at the top level (the record's `divergent`)
+    const bool leaf_div = REC && !ts;
     // min(1, exp(joint - joint0)): f64 by the division-free table form
     if constexpr (sizeof(T) == 8) ta = leaf_alpha_tab(joint - joint0, exp_lds, lek);
     else ta = rust_min1(gexp(joint - joint0));
@@ -1372,6 +1382,7 @@ void nuts_kernel(NutsLaunch a, TG tg_) {
 #pragma unroll
       for (int e = 0; e < E; ++e) q[e] = move ? pr[e] : q[e];
       acc += move ? 1 : 0;
+      if constexpr (REC) moved = moved || move;
       n += tn;
       bool s_ok = ts;
       {
@@ -1422,6 +1433,13 @@ void nuts_kernel(NutsLaunch a, TG tg_) {
 #ifdef GM_NUTS_PROF
     f_trans = true;
 #endif
+    // the transition's record (gm_launch.h StatsRec), before eps moves on:
+    // doublings 0 .. j-2 were whole (2^k leaves each), the last one ended at
+    // its leaf l
+    if constexpr (REC)
+      if (lane == 0)
+        stats_store<T>(a.stats, C, c, s, -joint0, alpha / (T)n_alpha, eps,
+                       stats_word((1ll << (j - 1)) + l, j, leaf_div, moved));
     const long long m = a.m0 + s + 1;
     T eta = (T)1 / (T)(m + t0c);
     h_bar = ((T)1 - eta) * h_bar + eta * (delta - alpha / (T)n_alpha);

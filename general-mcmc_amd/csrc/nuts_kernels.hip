@@ -447,7 +447,7 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
              uint64_t seed, uint64_t* step, uint32_t chain_offset, long long total,
              long long n_discard, int progress, long long steps_per_launch, hipStream_t st,
              std::vector<hipEvent_t>& evs, double* ms, long long* launches, const TrackLaunch* trk,
-             const StepHook* hook) {
+             const StepHook* hook, const StatsLaunch* stats) {
   const size_t esz = dt == GM_F32 ? 4 : 8;
   // progress == 2: NUTS::step (nuts.rs:431-433 -> generic_nuts.rs:755-925):
   // transitions that continue the chain state without init_chain_state, the
@@ -557,7 +557,7 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
   }
   for (long long li = 0; li < n_launch; ++li) {
     const long long start = seg_start[li], nst = seg_len[li];
-    NutsLaunch a;
+    NutsRecLaunch a;  // (the kernels that do not record take its NutsLaunch part)
     a.q = q;
     a.accepts = accepts;
     a.n_leapfrog = ns.n_leapfrog;
@@ -627,6 +627,11 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
     if (trk) {
       a.trk = *trk;
       a.trk.n0 = trk->n0 + (unsigned long long)start;
+    }
+    const bool rec = stats && stats->rec && !step_mode;
+    if (rec) {
+      a.stats = *stats;
+      a.stats.t0 = stats->t0 + start;
     }
     hipEventRecord(evs[2 * li], st);
     // the launch's momenta in one parallel pass ahead of the tree kernel
@@ -709,9 +714,9 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
       const size_t lds = nuts_size_lds(a, budget, blocks, 0, 1, D, esz);
       UserTargetArg ut{tg.params, tg.D};
       void* args[] = {&a, &ut};
-      e = jit_launch(JIT_NUTS, dt, tg, blocks, 256, lds, st, args);
+      e = jit_launch(rec ? JIT_NUTS_REC : JIT_NUTS, dt, tg, blocks, 256, lds, st, args);
     } else {
-      e = nuts_launch_layout(dt, tg, lay, a, st, budget);
+      e = nuts_launch_layout(dt, tg, lay, a, rec, st, budget);
     }
     ns.plan[0] = a.lds_levels;  // gm_nuts_get_plan
     ns.plan[1] = a.minv_lds;

@@ -104,14 +104,34 @@ hipError_t nuts_launch_part5(gm_dtype dt, const TargetDev& tg, const Layout& lay
 hipError_t nuts_launch_wide(gm_dtype dt, const TargetDev& tg, const Layout& lay, NutsLaunch& a, hipStream_t st,
                             const NutsLdsBudget& b, bool* found);
 bool nuts_wide_layout_supported(int lanes, int elems);
+// the same layouts' instantiations that write the per-transition records
+// (nuts_kernel REC; nuts_rec_part0.hip ... nuts_rec_part5.hip, nuts_wide_rec.hip)
+hipError_t nuts_launch_rec_part0(gm_dtype dt, const TargetDev& tg, const Layout& lay, NutsLaunch& a, hipStream_t st,
+                                 const NutsLdsBudget& b, bool* found);
+hipError_t nuts_launch_rec_part1(gm_dtype dt, const TargetDev& tg, const Layout& lay, NutsLaunch& a, hipStream_t st,
+                                 const NutsLdsBudget& b, bool* found);
+hipError_t nuts_launch_rec_part2(gm_dtype dt, const TargetDev& tg, const Layout& lay, NutsLaunch& a, hipStream_t st,
+                                 const NutsLdsBudget& b, bool* found);
+hipError_t nuts_launch_rec_part3(gm_dtype dt, const TargetDev& tg, const Layout& lay, NutsLaunch& a, hipStream_t st,
+                                 const NutsLdsBudget& b, bool* found);
+hipError_t nuts_launch_rec_part4(gm_dtype dt, const TargetDev& tg, const Layout& lay, NutsLaunch& a, hipStream_t st,
+                                 const NutsLdsBudget& b, bool* found);
+hipError_t nuts_launch_rec_part5(gm_dtype dt, const TargetDev& tg, const Layout& lay, NutsLaunch& a, hipStream_t st,
+                                 const NutsLdsBudget& b, bool* found);
+hipError_t nuts_launch_wide_rec(gm_dtype dt, const TargetDev& tg, const Layout& lay, NutsLaunch& a, hipStream_t st,
+                                const NutsLdsBudget& b, bool* found);
 
-inline hipError_t nuts_launch_layout(gm_dtype dt, const TargetDev& tg, const Layout& lay, NutsLaunch& a,
+// rec: the recording instantiations, `a` is then a NutsRecLaunch
+inline hipError_t nuts_launch_layout(gm_dtype dt, const TargetDev& tg, const Layout& lay, NutsLaunch& a, bool rec,
                                      hipStream_t st, const NutsLdsBudget& b) {
   using Fn = hipError_t (*)(gm_dtype, const TargetDev&, const Layout&, NutsLaunch&, hipStream_t,
                             const NutsLdsBudget&, bool*);
   static const Fn parts[] = {nuts_launch_part0, nuts_launch_part1, nuts_launch_part2, nuts_launch_part3,
                              nuts_launch_part4, nuts_launch_part5, nuts_launch_wide};
-  for (Fn f : parts) {
+  static const Fn rec_parts[] = {nuts_launch_rec_part0, nuts_launch_rec_part1, nuts_launch_rec_part2,
+                                 nuts_launch_rec_part3, nuts_launch_rec_part4, nuts_launch_rec_part5,
+                                 nuts_launch_wide_rec};
+  for (Fn f : rec ? rec_parts : parts) {
     bool found = false;
     const hipError_t e = f(dt, tg, lay, a, st, b, &found);
     if (found) return e;

@@ -5,14 +5,26 @@
 #include "nuts_device.h"
 #include "nuts_launch.h"
 
+// GM_NUTS_REC 1 (nuts_rec_partK.hip): the recording instantiations instead
+#ifndef GM_NUTS_REC
+#define GM_NUTS_REC 0
+#endif
+#if GM_NUTS_REC
+#define GM_NUTS_PART_FN nuts_launch_rec_part
+#else
+#define GM_NUTS_PART_FN nuts_launch_part
+#endif
 #define GM_NUTS_CAT2(a, b) a##b
 #define GM_NUTS_CAT(a, b) GM_NUTS_CAT2(a, b)
 
 namespace gm {
 
-hipError_t GM_NUTS_CAT(nuts_launch_part, GM_NUTS_PART)(gm_dtype dt, const TargetDev& tg, const Layout& lay,
-                                                       NutsLaunch& a, hipStream_t st, const NutsLdsBudget& b,
-                                                       bool* found) {
+hipError_t GM_NUTS_CAT(GM_NUTS_PART_FN, GM_NUTS_PART)(gm_dtype dt, const TargetDev& tg, const Layout& lay,
+                                                      NutsLaunch& a, hipStream_t st, const NutsLdsBudget& b,
+                                                      bool* found) {
+  constexpr bool REC = GM_NUTS_REC != 0;
+  // the kernel's argument block: the caller's NutsRecLaunch when recording
+  typename NutsLaunchOf<REC>::type& ka = static_cast<typename NutsLaunchOf<REC>::type&>(a);
   auto f = [&]<class T, int LPC, int E, class TG>(TG t) -> hipError_t {
     const long long threads = a.C * LPC;
     const unsigned blocks = (unsigned)((threads + 255) / 256);
@@ -22,16 +34,16 @@ hipError_t GM_NUTS_CAT(nuts_launch_part, GM_NUTS_PART)(gm_dtype dt, const Target
     // lives in LDS; nuts_run sets dense_frozen for it alone)
     if constexpr (LPC == 16 && E == 2) {
       if (a.mass_mode == 2 && a.dense_frozen) {
-        hipLaunchKernelGGL((nuts_kernel<T, LPC, E, TG, 3>), dim3(blocks), dim3(256), lds, st, a, t);
+        hipLaunchKernelGGL((nuts_kernel<T, LPC, E, TG, 3, REC>), dim3(blocks), dim3(256), lds, st, ka, t);
         return hipGetLastError();
       }
     }
     if (a.mass_mode == 2)
-      hipLaunchKernelGGL((nuts_kernel<T, LPC, E, TG, 2>), dim3(blocks), dim3(256), lds, st, a, t);
+      hipLaunchKernelGGL((nuts_kernel<T, LPC, E, TG, 2, REC>), dim3(blocks), dim3(256), lds, st, ka, t);
     else if (a.mass_mode == 1)
-      hipLaunchKernelGGL((nuts_kernel<T, LPC, E, TG, 1>), dim3(blocks), dim3(256), lds, st, a, t);
+      hipLaunchKernelGGL((nuts_kernel<T, LPC, E, TG, 1, REC>), dim3(blocks), dim3(256), lds, st, ka, t);
     else
-      hipLaunchKernelGGL((nuts_kernel<T, LPC, E, TG, 0>), dim3(blocks), dim3(256), lds, st, a, t);
+      hipLaunchKernelGGL((nuts_kernel<T, LPC, E, TG, 0, REC>), dim3(blocks), dim3(256), lds, st, ka, t);
     return hipGetLastError();
   };
   *found = false;
@@ -47,7 +59,7 @@ hipError_t GM_NUTS_CAT(nuts_launch_part, GM_NUTS_PART)(gm_dtype dt, const Target
 
 }  // namespace gm
 
-#if defined(GM_NUTS_PROF) && GM_NUTS_PART == 0
+#if defined(GM_NUTS_PROF) && GM_NUTS_PART == 0 && !GM_NUTS_REC
 // measurement build only: the per-wave iteration profile of the last NUTS
 // launch (nuts_device.h), n = waves x NPROF_SLOTS (43) unsigned 64-bit words
 extern "C" int gm_nuts_prof_read(void* out, long long n) {

@@ -13,8 +13,19 @@
 // X(LPC, E)
 #define GM_NUTS_WIDE_LAYOUTS(X) X(128, 4) X(256, 2) X(256, 4) X(512, 2)
 
+// GM_NUTS_REC 1 (nuts_wide_rec.hip): the recording instantiations instead
+#ifndef GM_NUTS_REC
+#define GM_NUTS_REC 0
+#endif
+#if GM_NUTS_REC
+#define GM_NUTS_WIDE_FN nuts_launch_wide_rec
+#else
+#define GM_NUTS_WIDE_FN nuts_launch_wide
+#endif
+
 namespace gm {
 
+#if !GM_NUTS_REC
 bool nuts_wide_layout_supported(int lanes, int elems) {
 #define GM_NW_OK(L_, E_) \
   if (lanes == L_ && elems == E_) return true;
@@ -22,16 +33,19 @@ bool nuts_wide_layout_supported(int lanes, int elems) {
 #undef GM_NW_OK
   return false;
 }
+#endif
 
 template <class T, int LPC, int E>
 static hipError_t launch_wide(const TargetDev& tg, NutsLaunch& a, hipStream_t st, const NutsLdsBudget& b) {
+  // the kernel's argument block: the caller's NutsRecLaunch when recording
+  typename NutsLaunchOf<GM_NUTS_REC != 0>::type& ka = static_cast<typename NutsLaunchOf<GM_NUTS_REC != 0>::type&>(a);
   auto go = [&]<class TG>(TG t) -> hipError_t {
     const unsigned blocks = (unsigned)a.C;  // one chain per block of LPC threads
     const size_t lds = nuts_size_lds(a, b, blocks, t.template lds_bytes<LPC, E>(), LPC, E, sizeof(T));
     if (a.mass_mode == 1)
-      hipLaunchKernelGGL((nuts_kernel<T, LPC, E, TG, 1>), dim3(blocks), dim3(LPC), lds, st, a, t);
+      hipLaunchKernelGGL((nuts_kernel<T, LPC, E, TG, 1, GM_NUTS_REC != 0>), dim3(blocks), dim3(LPC), lds, st, ka, t);
     else
-      hipLaunchKernelGGL((nuts_kernel<T, LPC, E, TG, 0>), dim3(blocks), dim3(LPC), lds, st, a, t);
+      hipLaunchKernelGGL((nuts_kernel<T, LPC, E, TG, 0, GM_NUTS_REC != 0>), dim3(blocks), dim3(LPC), lds, st, ka, t);
     return hipGetLastError();
   };
   if (a.mass_mode == 2) return hipErrorInvalidValue;  // (never: the launcher's layout choice)
@@ -56,7 +70,7 @@ static hipError_t launch_wide(const TargetDev& tg, NutsLaunch& a, hipStream_t st
   }
 }
 
-hipError_t nuts_launch_wide(gm_dtype dt, const TargetDev& tg, const Layout& lay, NutsLaunch& a, hipStream_t st,
+hipError_t GM_NUTS_WIDE_FN(gm_dtype dt, const TargetDev& tg, const Layout& lay, NutsLaunch& a, hipStream_t st,
                             const NutsLdsBudget& b, bool* found) {
   *found = false;
 #define GM_NW_TRY(L_, E_)                                                                         \

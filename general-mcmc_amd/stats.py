@@ -273,3 +273,111 @@ class MultiChainTracker:
             self.close()
         except Exception:
             pass
+
+
+# ---- per-transition sampler statistics (gm_sampler_set_stats) ----------------
+_STAT_FIELDS = {"energy": (0, None), "accept_stat": (1, None), "step_size": (2, None),
+                "n_leapfrog": (3, np.int32), "tree_depth": (4, np.int32),
+                "divergent": (5, np.bool_), "accepted": (6, np.bool_)}
+
+
+@dataclass
+class StatsSummary:
+    """The device reduction of a range of a run's sampler statistics
+    (SamplerStats.summary): per-chain arrays [n_chains] in f64 and the totals
+    over chains. E-BFMI = sum (E_n - E_{n-1})^2 / sum (E_n - mean E)^2."""
+    n_transitions: int
+    ebfmi: np.ndarray
+    n_divergent: np.ndarray
+    mean_accept_stat: np.ndarray
+    mean_n_leapfrog: np.ndarray
+    mean_tree_depth: np.ndarray
+    n_max_depth: np.ndarray
+    n_energy: np.ndarray
+    n_skipped: np.ndarray
+    total: dict
+
+    def __str__(self) -> str:
+        t = self.total
+        c, n = len(self.ebfmi), self.n_transitions
+        rows = [f"{n} transitions x {c} chains",
+                f"divergent transitions  {int(t['n_divergent'])} ({int((self.n_divergent > 0).sum())} chains)",
+                f"E-BFMI                 {t['ebfmi']:.4g} (lowest chain "
+                f"{np.nanmin(self.ebfmi) if np.isfinite(self.ebfmi).any() else float('nan'):.4g})",
+                f"mean accept_stat       {t['mean_accept_stat']:.4g}",
+                f"mean n_leapfrog        {t['mean_n_leapfrog']:.4g}",
+                f"mean tree_depth        {t['mean_tree_depth']:.4g}",
+                f"reached max_depth      {int(t['n_max_depth'])}",
+                f"non-finite energies    {int(t['n_skipped'])}"]
+        return "\n".join(rows)
+
+
+_SUMMARY_NAMES = ("ebfmi", "n_divergent", "mean_accept_stat", "mean_n_leapfrog", "mean_tree_depth",
+                  "n_max_depth", "n_energy", "n_skipped")
+
+
+class SamplerStats:
+    """The per-transition statistics of a sampler's last run (after
+    Sampler.collect_stats): arrays [n_chains, n_transitions], copied from the
+    device when first read. Stale, like DeviceSamples, once the sampler runs
+    again.
+
+    Transition n_warmup + k produced sample row first_row + k of the run;
+    first_row is 0, except after NUTS.run(n, 0), whose row 0 is the start
+    state and has no transition (first_row 1). In "collected" mode n_warmup is
+    0; in "all" mode the first n_warmup transitions are the discarded ones."""
+
+    def __init__(self, owner):
+        self.owner = owner
+        self.generation = owner._gen
+        n, fc, fr, rb = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
+        _lib.check(owner._lib.gm_sampler_stats_info(owner._h, C.byref(n), C.byref(fc), C.byref(fr), C.byref(rb)))
+        self.n_transitions, self.n_warmup, self.first_row, self.record_bytes = n.value, fc.value, fr.value, rb.value
+        self.n_chains = owner.n_chains
+        self._cache = {}
+
+    def _check_live(self):
+        if self.owner._h is None or self.generation != self.owner._gen:
+            raise RuntimeError("SamplerStats are stale: the sampler has run again (or was closed) "
+                               "since they were produced")
+
+    @property
+    def ptr(self) -> int:
+        """The records on the device, [n_transitions][n_chains] (gmcmc.h)."""
+        self._check_live()
+        p = C.c_void_p()
+        _lib.check(self.owner._lib.gm_sampler_stats_device(self.owner._h, C.byref(p)))
+        return p.value or 0
+
+    def _field(self, name: str) -> np.ndarray:
+        self._check_live()
+        if name not in self._cache:
+            code, dt = _STAT_FIELDS[name]
+            out = np.empty((self.n_chains, self.n_transitions), dtype=dt or self.owner.dtype)
+            _lib.check(self.owner._lib.gm_sampler_stats_field(self.owner._h, code, _lib.ptr(out)))
+            self._cache[name] = out
+        return self._cache[name]
+
+    energy = property(lambda self: self._field("energy"))
+    accept_stat = property(lambda self: self._field("accept_stat"))
+    step_size = property(lambda self: self._field("step_size"))
+    n_leapfrog = property(lambda self: self._field("n_leapfrog"))
+    tree_depth = property(lambda self: self._field("tree_depth"))
+    divergent = property(lambda self: self._field("divergent"))
+    accepted = property(lambda self: self._field("accepted"))
+
+    def summary(self, warmup: bool = False, rows: tuple[int, int] | None = None) -> StatsSummary:
+        """The reduction on the device of the collected transitions (with
+        warmup: of every recorded one; rows = (first, count): of that range)."""
+        self._check_live()
+        r0, n = rows if rows is not None else ((0, self.n_transitions) if warmup else
+                                               (self.n_warmup, self.n_transitions - self.n_warmup))
+        if n == 0 and 0 <= r0 <= self.n_transitions:
+            # nothing to reduce (e.g. a run that collected no row): zero counts, undefined ratios
+            z = {k: (0.0 if k.startswith("n_") else float("nan")) for k in _SUMMARY_NAMES}
+            return StatsSummary(0, *[np.full(self.n_chains, z[k]) for k in _SUMMARY_NAMES], z)
+        pc = np.empty((len(_SUMMARY_NAMES), self.n_chains), dtype=np.float64)
+        tot = np.empty(len(_SUMMARY_NAMES), dtype=np.float64)
+        _lib.check(self.owner._lib.gm_sampler_stats_reduce(self.owner._h, r0, n, _lib.ptr(pc), _lib.ptr(tot)))
+        return StatsSummary(int(n), *[pc[i] for i in range(len(_SUMMARY_NAMES))],
+                            {k: float(tot[i]) for i, k in enumerate(_SUMMARY_NAMES)})

@@ -302,6 +302,80 @@ int gm_get_logp(gm_sampler* s, void* out);
  * n_leapfrog per transition; NUTS: the tree sizes actually built; MH: 0). */
 int gm_get_leapfrog_counts(gm_sampler* s, int64_t* out);
 
+/* ---- Per-transition sampler statistics (HMC, NUTS) --------------------------
+ * No reference counterpart. mode 0 off (the default), 1 "collected": a record
+ * for every transition whose resulting state is a collected sample row,
+ * 2 "all": for every transition of a run, warm-up first. A run option, not
+ * sampler state: checkpoints (gm_state_save) do not contain it, and samples,
+ * counts, step sizes and metrics are bit for bit those of a run without it.
+ * gm_run, gm_run_device, gm_run_device_progress, gm_run_progress and
+ * gm_run_progress_cb record; gm_step does not. The records of a run are
+ * [n_transitions][n_chains] on the device, owned by the sampler and valid
+ * until its next run or destroy. GM_ESTATE for MH, GM_EINVAL for HMC on a wide
+ * layout (dim > 1024). A plain HMC sampler records through the kernel of the
+ * per-chain step sizes with the identity metric (the same bits).
+ *
+ * One record, of the sampler's dtype T (16 bytes f32, 32 bytes f64, aligned
+ * to its size):
+ *   T energy       K(p0) - logp(q) after the momentum refresh
+ *   T accept_stat  NUTS: alpha / n_alpha; HMC: min(1, exp(log_alpha)), NaN -> 0
+ *   T step_size    the step size the transition integrated with
+ *   word           uint32 (f32) / uint64 (f64, upper half 0):
+ *                  bits 0-23 n_leapfrog (saturates at 2^24 - 1), 24-29
+ *                  tree_depth (HMC 0), 30 divergent (NUTS: a leaf failed
+ *                  (logu - 1000) < joint; HMC: !(log_alpha > -1000)),
+ *                  31 accepted (the transition moved the chain) */
+int gm_sampler_set_stats(gm_sampler* s, int32_t mode);
+
+/* The last run's records: how many transitions were recorded, the index
+ * (within the records) of the first one whose resulting state is a collected
+ * sample row, the sample row that state is (0; 1 after a NUTS gm_run with
+ * n_discard 0, whose row 0 is the start state and has no transition) and the
+ * bytes of one record. Record first_collected + k belongs to sample row
+ * first_row + k. Any output may be NULL. GM_ESTATE when the last run recorded
+ * nothing (this and the getters below synchronise an asynchronous run first). */
+int gm_sampler_stats_info(gm_sampler* s, int64_t* n_transitions, int64_t* first_collected, int64_t* first_row,
+                          int32_t* record_bytes);
+/* The records on the device, [n_transitions][n_chains]. */
+int gm_sampler_stats_device(gm_sampler* s, const void** records);
+
+typedef enum {
+  GM_STAT_ENERGY = 0,      /* T */
+  GM_STAT_ACCEPT_STAT = 1, /* T */
+  GM_STAT_STEP_SIZE = 2,   /* T */
+  GM_STAT_N_LEAPFROG = 3,  /* int32 */
+  GM_STAT_TREE_DEPTH = 4,  /* int32 */
+  GM_STAT_DIVERGENT = 5,   /* uint8 */
+  GM_STAT_ACCEPTED = 6     /* uint8 */
+} gm_stat_field;
+/* One field of the last run's records on the host, [n_chains][n_transitions]. */
+int gm_sampler_stats_field(gm_sampler* s, int32_t field, void* out);
+
+/* The device reduction of record rows [row0, row0 + n_rows), in float64:
+ * per_chain [GM_STATS_FIELDS][n_chains] and the chains' totals
+ * total [GM_STATS_FIELDS] (either may be NULL). E-BFMI is
+ * sum (E_n - E_{n-1})^2 / sum (E_n - mean E)^2; its total pools the chains'
+ * sums, each about its own mean. Rows whose energy is not finite are counted
+ * (N_SKIPPED) and left out of both energy sums; a difference needs both of
+ * its adjacent rows finite. The other quantities take every row. */
+enum {
+  GM_STATS_EBFMI = 0,
+  GM_STATS_N_DIVERGENT = 1,
+  GM_STATS_MEAN_ACCEPT = 2,
+  GM_STATS_MEAN_LEAPFROG = 3,
+  GM_STATS_MEAN_DEPTH = 4,
+  GM_STATS_N_MAX_DEPTH = 5, /* transitions whose tree reached max_depth (HMC: 0) */
+  GM_STATS_N_ENERGY = 6,    /* rows with a finite energy */
+  GM_STATS_N_SKIPPED = 7,   /* rows without */
+  GM_STATS_FIELDS = 8
+};
+int gm_sampler_stats_reduce(gm_sampler* s, int64_t row0, int64_t n_rows, double* per_chain, double* total);
+/* The same reduction of records the caller holds on the device
+ * ([.][n_chains] of dtype's record). max_depth 0: nothing counts as having
+ * reached it. */
+int gm_stats_reduce_device(const void* records, gm_dtype dtype, int64_t n_chains, int64_t row0, int64_t n_rows,
+                           int32_t max_depth, double* per_chain, double* total);
+
 /* NUTS per-chain adaptation state: step size epsilon and epsilon_bar
  * (generic_nuts.rs:573-582). Pass NULL to skip either. */
 int gm_nuts_get_step_size(gm_sampler* s, double* eps, double* eps_bar);
