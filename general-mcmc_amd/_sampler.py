@@ -282,9 +282,16 @@ class Sampler:
         return self
 
     def set_unroll(self, n: int):
-        """HMC leapfrog-loop form: 0 automatic, or 1, 2, 4, 7 (the long count-down form); same results."""
+        """HMC leapfrog-loop form: 0 automatic, or 1, 2, 4, 7 (the long count-down form) or 49 (the
+        block form); same results."""
         _lib.check(self._lib.gm_sampler_set_unroll(self._h, int(n)))
         return self
+
+    def last_unroll(self) -> int:
+        """The leapfrog-loop form the last run's HMC launches took (the automatic choice resolved)."""
+        n = C.c_int32()
+        _lib.check(self._lib.gm_sampler_last_unroll(self._h, C.byref(n)))
+        return n.value
 
     def save_state(self) -> bytes:
         """Checkpoint (gm_state_save): positions, counters, seed and stream

@@ -365,6 +365,9 @@ template <class T, int E> struct RosenbrockLane;
 template <class T> struct RosenbrockT {
   T a, b, b2, b4;  // b2 = 2b, b4 = 4b (rounded once, host side)
   int D;
+  // the leapfrog body is a handful of instructions: hmc_kernel's block
+  // form (GM_LF_BLOCK of them straight-line) is compiled for this target
+  static constexpr bool lf_block = true;
   // per-lane view with the coordinate masks computed once per kernel
   template <int LPC, int E> __host__ __device__ size_t lds_bytes() const { return 0; }
   template <int LPC, int E> __device__ __forceinline__ RosenbrockLane<T, E> bind(int lane) const {

@@ -68,6 +68,12 @@ __device__ __forceinline__ void stats_store(const StatsLaunch& st, long long C, 
 // of GM_LF_LONG straight-line leapfrogs. The value is also the form's
 // lf_unroll / gm_sampler_set_unroll number.
 constexpr int GM_LF_LONG = 7;
+// The block form: (L - 1) % GM_LF_BLOCK leapfrogs as a binary ladder of
+// straight-line pieces, then (L - 1) / GM_LF_BLOCK count-down passes of
+// GM_LF_BLOCK straight-line leapfrogs (L = 50: one pass, no ladder). Compiled for one chain per wave at one element per lane and the
+// targets with `lf_block` (hmc_block_part.inc); every other kernel runs the
+// number as GM_LF_LONG, or as 1 where that is not compiled in either.
+constexpr int GM_LF_BLOCK = 49;
 
 struct HmcLaunch {
   void* q = nullptr;            // [C*D] state, in/out
@@ -84,7 +90,7 @@ struct HmcLaunch {
   int n_steps = 0;
   int collect_from = 0;         // steps s >= collect_from are stored ...
   long long sample_row0 = 0;    // ... at row sample_row0 + (s - collect_from)
-  int lf_unroll = 1;            // leapfrog loop form (1, 2, 4 or GM_LF_LONG; same results)
+  int lf_unroll = 1;            // leapfrog loop form (1, 2, 4, GM_LF_LONG or GM_LF_BLOCK; same results)
   void* zs = nullptr;           // wide layouts: momentum block scratch [C][S][lanes*elems]
 };
 

@@ -273,10 +273,11 @@ struct gm_sampler {
   bool lay_from_wide = false;  // NUTS: a wide layout replaced for a dense metric (gm_nuts_set_mass_adaptation)
   Layout lay_wide{};            // ... and that layout
   long long steps_per_launch = 1000;
-  int lf_unroll = 0;  // HMC leapfrog-loop form: 0 by the wave count and L (hmc_lf_unroll), else 1, 2, 4 or GM_LF_LONG
+  int lf_unroll = 0;  // HMC leapfrog-loop form: 0 by the wave count and L (hmc_lf_unroll), else 1, 2, 4, GM_LF_LONG or GM_LF_BLOCK
   std::vector<hipEvent_t> evs;
   double last_ms = 0;
   long long last_launches = 0;
+  int last_unroll = 0;  // the leapfrog loop form of the last run's launches (gm_sampler_last_unroll)
   bool last_ms_pending = false;  // HMC/MH: last_ms is read from evs[0..1] on request
   bool async_runs = false;       // HMC/MH runs return after enqueueing (gm_sampler_set_async)
   bool may_async = false;        // set by the entry points that honour async_runs
@@ -945,9 +946,16 @@ int gm_sampler_set_steps_per_launch(gm_sampler* s, int64_t steps) {
 
 int gm_sampler_set_unroll(gm_sampler* s, int32_t n) {
   GM_REQ(s, "sampler is NULL");
-  GM_REQ(n == 0 || n == 1 || n == 2 || n == 4 || n == GM_LF_LONG,
-         "unroll must be 0 (automatic), 1, 2, 4 or 7 (the long count-down form)");
+  GM_REQ(n == 0 || n == 1 || n == 2 || n == 4 || n == GM_LF_LONG || n == GM_LF_BLOCK,
+         "unroll must be 0 (automatic), 1, 2, 4, 7 (the long count-down form) or 49 (the block form)");
   s->lf_unroll = n;
+  return GM_OK;
+}
+
+int gm_sampler_last_unroll(gm_sampler* s, int32_t* n) {
+  GM_REQ(s, "sampler is NULL");
+  GM_REQ(n, "n is NULL");
+  *n = s->last_unroll;
   return GM_OK;
 }
 
@@ -976,7 +984,8 @@ int gm_sampler_last_run_stats(gm_sampler* s, double* kernel_ms, int64_t* launche
 // (tools/probe_hmc_scaling.py): x4 is ~12% faster while the grid has at most
 // one wave per SIMD (latency bound), and 10-20% slower from two waves per
 // SIMD up.
-static int hmc_lf_unroll(long long waves, long long L, bool has_long) {
+constexpr long long GM_LF_BLOCK_MIN_L1 = 2 * GM_LF_LONG;
+static int hmc_lf_unroll(long long waves, long long L, bool has_long, bool has_block) {
   static const int simds = [] {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -990,7 +999,13 @@ static int hmc_lf_unroll(long long waves, long long L, bool has_long) {
   // The long count-down form (GM_LF_LONG leapfrogs per trip) where x2 ran:
   // above one and up to four waves per SIMD, in the kernels that compile it
   // in (has_long), from the L at which its hot trips carry most of the steps.
-  if (form == 2 && has_long && L - 1 >= 2 * GM_LF_LONG) return GM_LF_LONG;
+  if (form == 2 && has_long && L - 1 >= 2 * GM_LF_LONG) {
+    // The block form (passes of GM_LF_BLOCK straight-line leapfrogs) where
+    // the kernel has it, from the L at which it measured no slower than the
+    // long form (GM_LF_BLOCK_MIN_L1: L = 20 is 1.7 % faster, profiles/r11).
+    if (has_block && L - 1 >= GM_LF_BLOCK_MIN_L1) return GM_LF_BLOCK;
+    return GM_LF_LONG;
+  }
   return form;
 }
 
@@ -1100,8 +1115,11 @@ static int run_steps(gm_sampler* s, long long total, long long collect_from, int
   // frozen mode with the identity state of StatsRun: the same bits)
   const bool adapt_path = s->ha.has || s->st.active;
   const bool has_long = !adapt_path && s->lay.lanes == 64 && s->lay.elems == 1;
+  // (the block form: hmc_part.inc, the targets with lf_block)
+  const bool has_block = has_long && s->tg.kind == GM_TARGET_ROSENBROCK;
   const int lf_unroll = s->kind != K_HMC ? 1 : s->lf_unroll ? s->lf_unroll
-                                                             : hmc_lf_unroll((s->C * s->lay.lanes + 63) / 64, s->L, has_long);
+                                                             : hmc_lf_unroll((s->C * s->lay.lanes + 63) / 64, s->L, has_long, has_block);
+  s->last_unroll = lf_unroll;
   if (s->kind == K_HMC && adapt_path) {
     const long long warm = s->ha.armed && s->ha.mode ? std::min(pending_warm, total) : 0;
     if (s->hd.on) return run_hmc_dense(s, total, collect_from, hook, chunk, lf_unroll, warm);

@@ -13,6 +13,9 @@ namespace gm {
 #ifndef GM_LF_U
 #define GM_LF_U GM_LF_LONG  // (measurement builds: the long form's trip length)
 #endif
+#ifndef GM_LF_BU
+#define GM_LF_BU GM_LF_BLOCK  // (measurement builds: the block form's pass length)
+#endif
 
 // a compile-time index handed to a generic lambda, and f(IntC<K>) for K < S
 template <int V> struct IntC { static constexpr int v = V; };
@@ -20,6 +23,13 @@ template <int K, int S, class F> __device__ __forceinline__ void for_each_k(F&& 
   if constexpr (K < S) {
     f(IntC<K>{});
     for_each_k<K + 1, S>(f);
+  }
+}
+// f(IntC<P>) for the powers of two P = 1 << B, 1 << (B + 1), ... below U
+template <int B, int U, class F> __device__ __forceinline__ void for_each_pow2_below(F&& f) {
+  if constexpr ((1 << B) < U) {
+    f(IntC<(1 << B)>{});
+    for_each_pow2_below<B + 1, U>(f);
   }
 }
 
@@ -44,7 +54,8 @@ __device__ __forceinline__ T accept_window(uint64_t seed, uint32_t ucid, uint64_
 
 // LF: the leapfrog loop form (1, 2 or 4 leapfrogs per trip, or GM_LF_LONG: the
 // long count-down form) as a constant, or 0 for the launch's a.lf_unroll (the
-// forms 1, 2 and 4 in the code; GM_LF_LONG then runs as 1).
+// forms 1, 2 and 4 in the code; GM_LF_LONG and GM_LF_BLOCK then run as 1),
+// or GM_LF_BLOCK: the block form (hmc_block_part.inc).
 //
 // One chain per wave (LPC = 64): the per-chain sums of a transition are left
 // in row 3 of the wave (lanes 48..63, group_sum_n_row3) and everything derived
@@ -199,12 +210,32 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
 #pragma unroll
       for (int e = 0; e < E; ++e) p1[e] = gfma(g1[e], half, p1[e]);
     };
-    // The long form: single steps bring L - 1 to a multiple of GM_LF_LONG
-    // (none at L = 50), then count-down trips of GM_LF_LONG straight-line
-    // leapfrogs: one scalar decrement, compare and taken branch per trip and
-    // no remainder test in it (7 taken branches per 49 leapfrogs where the x2
-    // form has 25, and 3 scalar instructions per 7 leapfrogs for 5 per 2).
-    if constexpr (LF == GM_LF_LONG) {
+    // The block form: count-down passes of GM_LF_BU straight-line leapfrogs,
+    // nothing scalar between them (L = 50: one pass), after the
+    // (L - 1) % GM_LF_BU others as a binary ladder of straight-line pieces of
+    // 1, 2, 4, ... leapfrogs, one wave-uniform bit test each, the whole ladder
+    // skipped when there is no remainder. (A switch into one block, entered
+    // at the position that leaves the remainder, is what this stands for: the
+    // compiler makes the fall-through of that switch a flag test and a branch
+    // in front of every leapfrog, profiles/r11/README.md.)
+    if constexpr (LF == GM_LF_BLOCK) {
+      const unsigned n1 = (unsigned)(a.L > 1 ? a.L - 1 : 0);
+      int passes = (int)(n1 / (unsigned)GM_LF_BU);
+      const int r = (int)n1 - passes * GM_LF_BU;
+      auto lfs = [&](auto nc) __attribute__((always_inline)) {
+        for_each_k<0, decltype(nc)::v>([&](auto) __attribute__((always_inline)) { lf(); });
+      };
+      if (r > 0)
+        for_each_pow2_below<0, GM_LF_BU>([&](auto pc) __attribute__((always_inline)) {
+          if (r & decltype(pc)::v) lfs(pc);
+        });
+      for (; passes > 0; --passes) lfs(IntC<GM_LF_BU>{});
+    } else if constexpr (LF == GM_LF_LONG) {
+      // The long form: single steps bring L - 1 to a multiple of GM_LF_LONG
+      // (none at L = 50), then count-down trips of GM_LF_LONG straight-line
+      // leapfrogs: one scalar decrement, compare and taken branch per trip and
+      // no remainder test in it (7 taken branches per 49 leapfrogs where the x2
+      // form has 25, and 3 scalar instructions per 7 leapfrogs for 5 per 2).
       const int n1 = a.L - 1;
       int trips = n1 > 0 ? (int)((unsigned)n1 / (unsigned)GM_LF_U) : 0;
       for (int r = n1 - trips * GM_LF_U; r > 0; --r) lf();

@@ -5,6 +5,9 @@
 #include "hmc_device.h"
 
 namespace gm {
+// hmc_kernel<T, 64, 1, RosenbrockT<T>, GM_LF_BLOCK> (hmc_block_f32.hip, hmc_block_f64.hip)
+hipError_t launch_hmc_block(const RosenbrockT<GM_HMC_T>& t, const HmcLaunch& a, hipStream_t st, LaunchEvents ev);
+
 hipError_t GM_HMC_NAME(const TargetDev& tg, const Layout& lay, const HmcLaunch& a, hipStream_t st,
                        LaunchEvents ev) {
   // (two chains per wave on packed f32 arithmetic, 13 VALU per two
@@ -19,7 +22,13 @@ hipError_t GM_HMC_NAME(const TargetDev& tg, const Layout& lay, const HmcLaunch& 
     // shapes): the leapfrog loop form is compiled in, so each of the S
     // unrolled block positions carries one form instead of three
     if constexpr (LPC == 64 && E <= 2) {
-      if (a.lf_unroll == GM_LF_LONG)
+      // the block form: one element per lane and the targets with
+      // lf_block, in a unit of its own (hmc_block_part.inc); elsewhere the
+      // number runs the long form
+      if constexpr (E == 1 && requires { TG::lf_block; }) {
+        if (a.lf_unroll == GM_LF_BLOCK) return launch_hmc_block(t, a, st, ev);
+      }
+      if (a.lf_unroll == GM_LF_LONG || a.lf_unroll == GM_LF_BLOCK)
         return launch_timed(hmc_kernel<T, LPC, E, TG, GM_LF_LONG>, dim3(blocks), dim3(256), lds, st, ev, a, t);
       if (a.lf_unroll == 4)
         return launch_timed(hmc_kernel<T, LPC, E, TG, 4>, dim3(blocks), dim3(256), lds, st, ev, a, t);

@@ -466,10 +466,15 @@ int gm_sampler_set_steps_per_launch(gm_sampler* s, int64_t steps);
 
 /* HMC leapfrog-loop form of the fused kernel: 0 (default) chosen by the
  * launch's waves per SIMD and L, or forced to 1, 2 or 4 leapfrogs per loop
- * trip or to 7, the long count-down form (7 per trip after (L - 1) % 7 single
- * ones; the kernels that do not compile it in run it as 1). Tests and
- * measurements; identical results in every form. No reference counterpart. */
+ * trip, to 7, the long count-down form (7 per trip after (L - 1) % 7 single
+ * ones; the kernels that do not compile it in run it as 1), or to 49, the
+ * block form ((L - 1) % 49 leapfrogs as straight-line pieces of 1, 2, 4, ...,
+ * then count-down passes of 49 straight-line ones; the kernels that do not
+ * compile it in run it as 7, or as 1). Tests and measurements; identical
+ * results in every form. No reference counterpart. */
 int gm_sampler_set_unroll(gm_sampler* s, int32_t n);
+/* The form the last run's HMC launches took (the automatic choice resolved). */
+int gm_sampler_last_unroll(gm_sampler* s, int32_t* n);
 
 /* Pre-size the device sample buffer for runs collecting up to n_collect
  * transitions, so that a later gm_run / gm_run_device does no device
