@@ -106,6 +106,9 @@ SIGNATURES = {
     "gm_stats_reduce_device": (_ip, [_vp, _ip, _i64, _i64, _i64, _i32, _vp, _vp]),
     "gm_nuts_get_step_size": (_ip, [_vp, _vp, _vp]),
     "gm_nuts_set_mass_adaptation": (_ip, [_vp, _i32, _i64, _i64, _i64, _dbl, _dbl, _i64]),
+    "gm_nuts_set_metric_convention": (_ip, [_vp, _i32, _i32]),
+    "gm_nuts_get_pooled_metric": (_ip, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "gm_nuts_set_pooled_metric": (_ip, [_vp, _vp]),
     "gm_nuts_set_lds_levels": (_ip, [_vp, _i32]),
     "gm_nuts_set_dense_forms": (_ip, [_vp, _i32, _i32]),
     "gm_nuts_get_plan": (_ip, [_vp, _vp, _i32]),

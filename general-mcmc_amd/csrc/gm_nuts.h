@@ -46,7 +46,28 @@ struct NutsState {
   void* rm2d = nullptr;       // [C][D]
   void* rm2 = nullptr;        // [C][D][D]
   int* updated = nullptr;     // [C]
-  void* mscratch = nullptr;   // [C][4][D][D] dense update workspace
+  void* mscratch = nullptr;   // [C][4 + convention][D][D] dense update workspace
+  // metric convention (gm_nuts_set_metric_convention): 0 the reference's
+  // M = Sigma_hat, 1 whitening M^-1 = Sigma_hat; pooled: one Sigma_hat from
+  // all chains' window rows (whitening, 2 <= D <= 64), in float64
+  int convention = 0, pooled = 0;
+  // allocated while convention == 1 and 2 <= D <= 64:
+  double* pool = nullptr;      // Sigma_hat [D][D], chol(Sigma_hat^-1) [D][D] (the masters), sig_in [D][D],
+                               // then the open window's c0 [D], s1 [D], S2 [D][D]
+  long long* pcount = nullptr; // updates, failed, the open window's rows (set when a checkpoint is written), 0
+  int* pok = nullptr;          // the last window kernel's outcome
+  void* pcopy = nullptr;       // the masters rounded to the sampler dtype, 2 [D][D]
+  long long p_rn = 0;          // rows in the open window's pooled statistics
+  void* slab = nullptr;        // a warm-up launch's window rows [rows][C][D]
+  void* ppart = nullptr;       // Gram partials (hmc_dense_gram_part_bytes)
+  size_t slab_bytes = 0, ppart_bytes = 0;
+  double* p_sig() const { return pool; }
+  double* p_lp(int D) const { return pool + (size_t)D * D; }
+  double* p_in(int D) const { return pool + 2 * (size_t)D * D; }
+  double* p_c0(int D) const { return pool + 3 * (size_t)D * D; }
+  double* p_s1(int D) const { return pool + 3 * (size_t)D * D + D; }
+  double* p_S2(int D) const { return pool + 3 * (size_t)D * D + 2 * (size_t)D; }
+  static size_t pool_doubles(int D) { return 4 * (size_t)D * D + 2 * (size_t)D; }
   void* zbuf = nullptr;       // [steps][C][D] momentum normals of a launch (nuts_momenta_kernel)
   bool momentum_pass = true;  // gm_nuts_set_momentum_pass
 #ifndef GM_NUTS_ZBUF_MAX
@@ -74,6 +95,15 @@ int nuts_set_mass(NutsState* ns, gm_dtype dt, long long C, int D, int mode, long
                   long long end_buffer, long long initial_window, double regularize, double jitter);
 int nuts_get_mass(NutsState& ns, gm_dtype dt, long long C, int D, int32_t* kind, void* dinv, void* dsqrt,
                   void* minv, void* mchol);
+// the metric convention of the window ends from now on; allocates or frees
+// the pooled state; the sampler is unchanged on an error
+int nuts_set_convention(NutsState* ns, gm_dtype dt, long long C, int D, int convention, int pooled);
+// the float64 masters [D][D] and the counters (any may be null)
+int nuts_get_pooled(NutsState& ns, int D, double* sigma, double* chol_prec, long long* updates,
+                    long long* failed);
+// sigma [D][D] (validated by the caller) as every chain's dense whitening
+// metric, factored by the window-end kernel; waits for the stream
+int nuts_set_pooled_metric(NutsState& ns, gm_dtype dt, long long C, int D, const double* sigma, hipStream_t st);
 int nuts_get_step_size(NutsState& ns, gm_dtype dt, long long C, double* eps, double* eps_bar);
 int nuts_get_leapfrogs(NutsState& ns, long long C, long long* out);
 

@@ -2233,6 +2233,66 @@ int gm_nuts_set_mass_adaptation(gm_sampler* s, int32_t mode, int64_t start_buffe
   return GM_OK;
 }
 
+int gm_nuts_set_metric_convention(gm_sampler* s, int32_t convention, int32_t pooled) {
+  GM_REQ(s, "sampler is NULL");
+  GM_REQ(s->kind == K_NUTS, "not a NUTS sampler");
+  GM_REQ(convention == 0 || convention == 1, "convention must be 0 (reference) or 1 (whitening)");
+  GM_REQ(pooled == 0 || pooled == 1, "pooled must be 0 or 1");
+  GM_REQ(!pooled || convention == 1, "a pooled metric needs the whitening convention");
+  GM_REQ(!pooled || (s->D >= 2 && s->D <= GM_DENSE_MAX_DIM), "a pooled metric needs 2 <= dim <= 64");
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  return nuts_set_convention(&s->nuts, s->dt, s->C, s->D, convention, pooled);
+}
+
+int gm_nuts_get_pooled_metric(gm_sampler* s, double* sigma, double* chol_prec, int64_t* updates, int64_t* failed) {
+  GM_REQ(s, "sampler is NULL");
+  GM_REQ(s->kind == K_NUTS, "not a NUTS sampler");
+  if (!s->nuts.pool) {
+    set_error("the sampler keeps no pooled metric (gm_nuts_set_metric_convention: whitening, 2 <= dim <= 64)");
+    return GM_ESTATE;
+  }
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  long long u = 0, f = 0;
+  const int rc = nuts_get_pooled(s->nuts, s->D, sigma, chol_prec, &u, &f);
+  if (rc) return rc;
+  if (updates) *updates = u;
+  if (failed) *failed = f;
+  return GM_OK;
+}
+
+int gm_nuts_set_pooled_metric(gm_sampler* s, const double* sigma) {
+  GM_REQ(s, "sampler is NULL");
+  GM_REQ(s->kind == K_NUTS, "not a NUTS sampler");
+  GM_REQ(sigma, "sigma is NULL");
+  if (s->nuts.mass_mode != 2 || s->nuts.convention != 1 || !s->nuts.pool) {
+    set_error("gm_nuts_set_pooled_metric needs a dense metric with the whitening convention "
+              "(gm_nuts_set_metric_convention, gm_nuts_set_mass_adaptation mode 2; 2 <= dim <= 64)");
+    return GM_ESTATE;
+  }
+  const size_t D = (size_t)s->D;
+  // checked in full before anything changes: finite, symmetric, and positive
+  // definite by the factorisation the window kernel runs (same operations)
+  for (size_t i = 0; i < D * D; ++i) GM_REQ(std::isfinite(sigma[i]), "sigma entries must be finite");
+  for (size_t i = 0; i < D; ++i)
+    for (size_t j = 0; j < i; ++j) GM_REQ(sigma[i * D + j] == sigma[j * D + i], "sigma must be symmetric");
+  {
+    std::vector<double> l(sigma, sigma + D * D);
+    for (size_t k = 0; k < D; ++k) {
+      const double piv = l[k * D + k];
+      GM_REQ(piv > 0 && std::isfinite(piv), "sigma must be positive definite");
+      const double lkk = std::sqrt(piv);
+      for (size_t i = k + 1; i < D; ++i) l[i * D + k] = l[i * D + k] / lkk;
+      for (size_t i = k + 1; i < D; ++i)
+        for (size_t j = k + 1; j <= i; ++j) l[i * D + j] = l[i * D + j] - l[i * D + k] * l[j * D + k];
+    }
+  }
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  return nuts_set_pooled_metric(s->nuts, s->dt, s->C, s->D, sigma, s->stream);
+}
+
 int gm_nuts_set_momentum_pass(gm_sampler* s, int32_t on) {
   GM_REQ(s, "sampler is NULL");
   GM_REQ(s->kind == K_NUTS, "not a NUTS sampler");
@@ -2329,8 +2389,13 @@ struct StatePart {
 // the blob's parts for a sampler of this kind / shape / metric mode; sizes
 // only depend on the header fields, so a blob can be validated before any
 // state is touched
+// (NUTS: mass_mode carries the metric convention above its low byte -- bit 8
+// whitening, bit 9 pooled, bit 10 the pooled state follows -- so a sampler
+// with the reference convention writes what it always did)
 std::vector<StatePart> state_parts_for(gm_sampler* s, int mass_mode) {
   const size_t C = (size_t)s->C, D = (size_t)s->D, e = s->esz;
+  const int nuts_flags = s->kind == K_NUTS ? mass_mode >> 8 : 0;
+  if (s->kind == K_NUTS) mass_mode &= 0xff;
   std::vector<StatePart> v{{s->d_q, C * D * e}, {s->d_acc, C * sizeof(long long)}};
   if (s->kind == K_NUTS) {
     NutsState& n = s->nuts;
@@ -2347,6 +2412,10 @@ std::vector<StatePart> state_parts_for(gm_sampler* s, int mass_mode) {
     if (mass_mode == 2) {
       v.push_back({n.minv, C * D * D * e});
       v.push_back({n.mchol, C * D * D * e});
+    }
+    if (nuts_flags & 4) {  // the float64 masters, the open window's pooled statistics, the counters
+      v.push_back({n.pool, NutsState::pool_doubles((int)D) * sizeof(double)});
+      v.push_back({n.pcount, 4 * sizeof(long long)});
     }
   }
   if (s->kind == K_HMC && mass_mode) {
@@ -2371,7 +2440,10 @@ size_t parts_bytes(const std::vector<StatePart>& v) {
   return b;
 }
 int state_mode(gm_sampler* s) {
-  return s->kind == K_NUTS ? s->nuts.mass_mode : s->kind == K_HMC && s->ha.has ? (s->hd.on ? 2 : 1) : 0;
+  if (s->kind == K_NUTS)
+    return s->nuts.mass_mode |
+           ((s->nuts.convention ? 1 : 0) | (s->nuts.pooled ? 2 : 0) | (s->nuts.pool ? 4 : 0)) << 8;
+  return s->kind == K_HMC && s->ha.has ? (s->hd.on ? 2 : 1) : 0;
 }
 size_t state_bytes(gm_sampler* s) { return parts_bytes(state_parts_for(s, state_mode(s))); }
 }  // namespace
@@ -2444,7 +2516,9 @@ int gm_state_save(gm_sampler* s, void* out, uint64_t bytes) {
   h.max_depth = s->max_depth;
   if (s->kind == K_NUTS) {
     const NutsState& n = s->nuts;
-    h.mass_mode = n.mass_mode;
+    h.mass_mode = state_mode(s);
+    if (n.pool)  // the open window's row count travels with the counters
+      GM_HIP(hipMemcpy(n.pcount + 2, &n.p_rn, sizeof(long long), hipMemcpyHostToDevice));
     h.m_sb = n.m_sb;
     h.m_eb = n.m_eb;
     h.sched_next = n.sched_next;
@@ -2511,7 +2585,14 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
     case K_NUTS:
       GM_REQ(h.target_accept == s->target_accept && h.max_depth == s->max_depth,
              "state blob is for a different target_accept_p / max_depth");
-      GM_REQ(h.mass_mode >= 0 && h.mass_mode <= 2, "corrupt state blob (mass mode)");
+      GM_REQ(h.mass_mode >= 0 && (h.mass_mode & 0xff) <= 2 && (h.mass_mode >> 8) <= 7,
+             "corrupt state blob (mass mode)");
+      {  // pooled needs whitening; the pooled state is there exactly when whitening can pool at this dim
+        const int fl = h.mass_mode >> 8;
+        const bool can_pool = s->D >= 2 && s->D <= GM_DENSE_MAX_DIM;
+        GM_REQ((!(fl & 2) || ((fl & 1) && can_pool)) && ((fl & 4) != 0) == ((fl & 1) && can_pool),
+               "corrupt state blob (metric convention)");
+      }
       GM_REQ(h.nuts_m >= 0 && h.nuts_n_discard >= 0 && h.sched_len >= 0, "corrupt state blob (counters)");
       break;
   }
@@ -2519,10 +2600,16 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
   GM_REQ(bytes >= parts_bytes(state_parts_for(s, h.mass_mode)), "state blob too short");
   GM_HIP(hipSetDevice(s->device));
   GM_HIP(hipStreamSynchronize(s->stream));
-  if (s->kind == K_NUTS && (h.mass_mode != s->nuts.mass_mode || h.mass_mode)) {
-    const int rc = nuts_set_mass(&s->nuts, s->dt, s->C, s->D, h.mass_mode, h.m_sb, h.m_eb, 0,
-                                 h.m_reg, h.m_jit);
-    if (rc) return rc;
+  if (s->kind == K_NUTS) {
+    const int mm = h.mass_mode & 0xff, fl = h.mass_mode >> 8;
+    if ((fl & 1) != s->nuts.convention || ((fl >> 1) & 1) != s->nuts.pooled) {
+      const int rc = nuts_set_convention(&s->nuts, s->dt, s->C, s->D, fl & 1, (fl >> 1) & 1);
+      if (rc) return rc;
+    }
+    if (mm != s->nuts.mass_mode || mm) {
+      const int rc = nuts_set_mass(&s->nuts, s->dt, s->C, s->D, mm, h.m_sb, h.m_eb, 0, h.m_reg, h.m_jit);
+      if (rc) return rc;
+    }
   }
   if (s->kind == K_HMC) {
     if (h.mass_mode) {
@@ -2547,6 +2634,8 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
     s->nuts.sched_len = h.sched_len;
     s->nuts.m = h.nuts_m;
     s->nuts.n_discard = h.nuts_n_discard;
+    if (s->nuts.pool)
+      GM_HIP(hipMemcpy(&s->nuts.p_rn, s->nuts.pcount + 2, sizeof(long long), hipMemcpyDeviceToHost));
   }
   if (s->kind == K_HMC && h.mass_mode) {
     HmcAdapt& a = s->ha;

@@ -1,3 +1,4 @@
+#include <algorithm>
 #include <cstdlib>
 #include <cstdio>
 // nuts_kernels.hip — many-chain No-U-Turn sampler for gfx950.
@@ -84,11 +85,17 @@ __device__ void diag_from_var(const T* var, int D, T jitter, T* inv, T* sq) {  /
   }
 }
 
+// whiten 0: the reference's convention, M = cov (inv = cov^-1 for the kinetic
+// energy and the drift, chol(cov) / sqrt(var) for the momentum). whiten 1:
+// M^-1 = cov (inv = cov, the momentum factor chol(cov^-1) / 1/sqrt(var)): the
+// same statistics, floors and jitter tries; the tree kernels take either as
+// the same pair of operators.
 template <class T>
-__global__ void nuts_mass_update_kernel(long long C, int D, int mode, double regularize, double jitter_cfg,
-                                        int* __restrict__ mkind, T* dinv, T* dsq, T* minv, T* mchol,
-                                        int* __restrict__ rn, T* rmean, T* rm2d, T* rm2,
-                                        int* __restrict__ updated, T* scratch /* [C][4][D][D] */) {
+__global__ void nuts_mass_update_kernel(long long C, int D, int mode, int whiten, double regularize,
+                                        double jitter_cfg, int* __restrict__ mkind, T* dinv, T* dsq, T* minv,
+                                        T* mchol, int* __restrict__ rn, T* rmean, T* rm2d, T* rm2,
+                                        int* __restrict__ updated,
+                                        T* scratch /* [C][4 + whiten][D][D] */) {
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   updated[c] = 0;
@@ -106,11 +113,16 @@ __global__ void nuts_mass_update_kernel(long long C, int D, int mode, double reg
     const T* m2d = rm2d + c * D;
     for (int i = 0; i < D; ++i) var[i] = rust_max(omr * (m2d[i] / nd) + reg, jitter);
     diag_from_var(var, D, jitter, di, ds);
+    if (whiten)  // v through diag_from_var's floor: inv = v, sqrt = 1 / sqrt(v)
+      for (int i = 0; i < D; ++i) {
+        di[i] = rust_max(var[i], jitter);
+        ds[i] = (T)1 / ds[i];
+      }
     mkind[c] = 1;
     ok = true;
   } else {
     const long long DD = (long long)D * D;
-    T* cov = scratch + c * 4 * DD;
+    T* cov = scratch + c * (4 + whiten) * DD;
     T* tr = cov + DD;
     T* chol = tr + DD;
     T* il = chol + DD;
@@ -128,8 +140,16 @@ __global__ void nuts_mass_update_kernel(long long C, int D, int mode, double reg
     for (int t = 0; t < 8 && !ok; ++t) {
       for (long long k = 0; k < DD; ++k) tr[k] = cov[k];
       for (int d = 0; d < D; ++d) tr[d * D + d] = tr[d * D + d] + jj;
-      if (cholesky_spd(tr, D, chol) && invert_spd_from_cholesky(chol, D, tr, il)) ok = true;
-      else jj = jj * (T)10;
+      if (!whiten) {
+        if (cholesky_spd(tr, D, chol) && invert_spd_from_cholesky(chol, D, tr, il)) ok = true;
+        else jj = jj * (T)10;
+      } else {  // tr stays the jittered covariance; chol becomes the factor of its inverse
+        T* prec = il + DD;
+        if (cholesky_spd(tr, D, chol) && invert_spd_from_cholesky(chol, D, prec, il) &&
+            cholesky_spd(prec, D, chol))
+          ok = true;
+        else jj = jj * (T)10;
+      }
     }
     if (ok) {
       for (long long k = 0; k < DD; ++k) {
@@ -141,6 +161,11 @@ __global__ void nuts_mass_update_kernel(long long C, int D, int mode, double reg
       T* var = cov;
       for (int i = 0; i < D; ++i) var[i] = (T)1;
       diag_from_var(var, D, jitter, di, ds);
+      if (whiten)
+        for (int i = 0; i < D; ++i) {
+          di[i] = rust_max(var[i], jitter);
+          ds[i] = (T)1 / ds[i];
+        }
       mkind[c] = 1;
       ok = true;
     }
@@ -155,6 +180,203 @@ __global__ void nuts_mass_update_kernel(long long C, int D, int mode, double reg
     if (mode == 2)
       for (long long k = 0; k < (long long)D * D; ++k) rm2[c * (long long)D * D + k] = (T)0;
   }
+}
+
+// ---- pooled whitening metric ---------------------------------------------------
+// A window end of the pooled metric (or, from_stats 0, a metric set from
+// outside: sg then holds Sigma already). One workgroup, float64.
+// from_stats: sg holds S2 and becomes Sigma = (1 - reg) S + reg I with the
+// diagonal floored at max(jitter, 1e-10), S = (S2 - s1 s1^T / n) / (n - 1);
+// the upper triangle is computed and mirrored, so Sigma is exactly symmetric.
+// mode 2: Lc = chol(Sigma) in place in LDS (right-looking), X = Lc^-1 by
+// forward substitution (one thread per column, kept transposed in the strict
+// upper triangle), P = X^T X for j <= i and mirrored, Lp = chol(P) in place in
+// a second LDS matrix (Sigma itself stays in global memory: three matrices do
+// not fit). mode 1: v = diag(Sigma), its factor 1 / sqrt(v). A non-positive or
+// non-finite pivot of either factorisation leaves the masters as they were
+// (counters[1] when count). On success the masters and their copies rounded
+// once to T are written (mode 1: the D diagonal entries lead each array) and
+// *okflag = 1; nuts_pooled_apply_kernel hands the copies to the chains.
+// from_stats: s1 and S2 are zeroed at the end.
+template <class T>
+__global__ __launch_bounds__(256) void nuts_pooled_window_kernel(
+    int D, int mode, int from_stats, long long n, double reg, double jitter_cfg, double* __restrict__ s1,
+    double* __restrict__ sg, double* __restrict__ sig64, double* __restrict__ lp64, T* __restrict__ tsig,
+    T* __restrict__ tlp, long long* __restrict__ counters, int count, int* __restrict__ okflag) {
+  __shared__ double W[64 * 64];  // lower + diagonal: Lc; strictly upper: X^T
+  __shared__ double P[64 * 64];  // Sigma^-1, then its factor in the lower triangle
+  __shared__ double xd[64];      // diagonal of X = 1 / Lc_ii
+  __shared__ int fail;
+  const int tid = threadIdx.x;
+  if (tid == 0) fail = 0;
+  const double fl = jitter_cfg > 1e-10 ? jitter_cfg : 1e-10;
+  const double nd = (double)n;
+  for (int idx = tid; idx < D * D; idx += 256) {
+    const int i = idx / D, j = idx - i * D;
+    if (from_stats) {
+      if (j < i) continue;  // (the mirror image is written by (j, i))
+      const double s = (sg[idx] - s1[i] * s1[j] / nd) / (nd - 1.0);
+      double v = (1.0 - reg) * s + (i == j ? reg : 0.0);
+      if (i == j) v = (v < fl) ? fl : v;
+      sg[idx] = v;
+      sg[j * D + i] = v;
+      W[idx] = v;
+      W[j * D + i] = v;
+    } else {
+      W[idx] = sg[idx];
+    }
+  }
+  __syncthreads();
+  auto chol_in_place = [&](double* A) {  // lower triangle of A; sets fail
+    for (int k = 0; k < D; ++k) {
+      if (tid == 0) {
+        const double piv = A[k * D + k];
+        if (!(piv > 0.0) || !(piv < __builtin_inf())) fail = 1;
+        else A[k * D + k] = __builtin_sqrt(piv);
+      }
+      __syncthreads();
+      if (fail) break;  // block-uniform: read after the barrier
+      const double lkk = A[k * D + k];
+      __syncthreads();
+      for (int i = k + 1 + tid; i < D; i += 256) A[i * D + k] = A[i * D + k] / lkk;
+      __syncthreads();
+      const int m = D - k - 1;
+      for (int idx = tid; idx < m * m; idx += 256) {
+        const int i = k + 1 + idx / m, j = k + 1 + idx % m;
+        if (j <= i) A[i * D + j] = A[i * D + j] - A[i * D + k] * A[j * D + k];
+      }
+      __syncthreads();
+    }
+    __syncthreads();
+  };
+  if (mode == 1) {
+    if (tid < D) {
+      const double v = W[tid * D + tid];
+      if (!(v > 0.0) || !(v < __builtin_inf())) fail = 1;  // (any failing thread writes the same 1)
+    }
+    __syncthreads();
+  } else {
+    chol_in_place(W);
+    if (!fail) {
+      if (tid < D) {  // column tid of X = Lc^-1, stored as row tid of the strictly upper part
+        const int j = tid;
+        const double xjj = 1.0 / W[j * D + j];
+        xd[j] = xjj;
+        for (int i = j + 1; i < D; ++i) {
+          double s = W[i * D + j] * xjj;
+          for (int k = j + 1; k < i; ++k) s += W[i * D + k] * W[j * D + k];
+          W[j * D + i] = -s / W[i * D + i];
+        }
+      }
+      __syncthreads();
+      for (int idx = tid; idx < D * D; idx += 256) {  // P_ij = sum_{k >= i} X_ki X_kj, j <= i
+        const int i = idx / D, j = idx - i * D;
+        if (j > i) continue;
+        double s = xd[i] * (i == j ? xd[j] : W[j * D + i]);
+        for (int k = i + 1; k < D; ++k) s += W[i * D + k] * W[j * D + k];
+        P[idx] = s;
+        P[j * D + i] = s;
+      }
+      __syncthreads();
+      chol_in_place(P);
+    }
+  }
+  const bool ok = !fail;
+  if (ok) {
+    if (mode == 1) {
+      for (int idx = tid; idx < D * D; idx += 256) {
+        const int i = idx / D, j = idx - i * D;
+        const double v = W[i * D + i];
+        sig64[idx] = i == j ? v : 0.0;
+        lp64[idx] = i == j ? 1.0 / __builtin_sqrt(v) : 0.0;
+        if (i == j) {
+          tsig[i] = (T)v;
+          tlp[i] = (T)(1.0 / __builtin_sqrt(v));
+        }
+      }
+    } else {
+      for (int idx = tid; idx < D * D; idx += 256) {
+        const int i = idx / D, j = idx - i * D;
+        const double l = j <= i ? P[idx] : 0.0;
+        const double v = sg[idx];
+        sig64[idx] = v;
+        tsig[idx] = (T)v;
+        lp64[idx] = l;
+        tlp[idx] = (T)l;
+      }
+    }
+  }
+  if (tid == 0) {
+    *okflag = ok ? 1 : 0;
+    if (count) counters[ok ? 0 : 1] += 1;
+  }
+  if (from_stats) {
+    __syncthreads();  // (sg is S2: read above)
+    for (int idx = tid; idx < D * D; idx += 256) sg[idx] = 0.0;
+    if (tid < D) s1[tid] = 0.0;
+  }
+}
+
+// The window kernel's outcome for every chain: on success the rounded copies
+// into each chain's slots (kind = mode) and updated = mark, so that the next
+// launch re-finds epsilon as after a per-chain update; otherwise updated = 0.
+// reset: the per-chain Welford state is zeroed either way.
+template <class T>
+__global__ void nuts_pooled_apply_kernel(long long C, int D, int mode, const int* __restrict__ okflag,
+                                         const T* __restrict__ tsig, const T* __restrict__ tlp,
+                                         int* __restrict__ mkind, T* __restrict__ dinv, T* __restrict__ dsq,
+                                         T* __restrict__ minv, T* __restrict__ mchol, int* __restrict__ rn,
+                                         T* __restrict__ rmean, T* __restrict__ rm2d, T* __restrict__ rm2,
+                                         int* __restrict__ updated, int reset, int mark) {
+  const bool ok = *okflag != 0;
+  const long long dd = (long long)D * D;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long k0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (mode == 2)
+    for (long long k = k0; k < C * dd; k += stride) {
+      const long long r = k % dd;
+      if (ok) {
+        minv[k] = tsig[r];
+        mchol[k] = tlp[r];
+      }
+      if (reset) rm2[k] = (T)0;
+    }
+  for (long long k = k0; k < C * D; k += stride) {
+    if (ok && mode == 1) {
+      const int i = (int)(k % D);
+      dinv[k] = tsig[i];
+      dsq[k] = tlp[i];
+    }
+    if (reset) {
+      rmean[k] = (T)0;
+      rm2d[k] = (T)0;
+    }
+  }
+  for (long long c = k0; c < C; c += stride) {
+    if (ok) mkind[c] = mode;
+    updated[c] = (ok && mark) ? 1 : 0;
+    if (reset) rn[c] = 0;
+  }
+}
+
+template <class T>
+static hipError_t pooled_window_launch(NutsState& ns, long long C, int D, int from_stats, long long n, int count,
+                                       int mark, hipStream_t st) {
+  const size_t dd = (size_t)D * D;
+  T* tsig = (T*)ns.pcopy;
+  T* tlp = tsig + dd;
+  hipLaunchKernelGGL(nuts_pooled_window_kernel<T>, dim3(1), dim3(256), 0, st, D, ns.mass_mode, from_stats, n,
+                     ns.m_reg, ns.m_jit, ns.p_s1(D), from_stats ? ns.p_S2(D) : ns.p_in(D), ns.p_sig(), ns.p_lp(D),
+                     tsig, tlp, ns.pcount, count, ns.pok);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const long long work = C * (long long)(ns.mass_mode == 2 ? dd : (size_t)D);
+  const unsigned blocks = (unsigned)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192);
+  hipLaunchKernelGGL(nuts_pooled_apply_kernel<T>, dim3(blocks), dim3(256), 0, st, C, D, ns.mass_mode,
+                     (const int*)ns.pok, (const T*)tsig, (const T*)tlp, ns.mkind, (T*)ns.dinv, (T*)ns.dsq,
+                     (T*)ns.minv, (T*)ns.mchol, ns.rn, (T*)ns.rmean, (T*)ns.rm2d, (T*)ns.rm2, ns.updated,
+                     from_stats, mark);
+  return hipGetLastError();
 }
 
 // The transition momenta of a NUTS launch as standard normals, out[s][c][i]
@@ -363,9 +585,115 @@ static void mass_free(NutsState* ns) {
   ns->mass_mode = 0;
 }
 
+static void pool_free(NutsState* ns) {
+  ffree(ns->pool);
+  ffree(ns->pcount);
+  ffree(ns->pok);
+  ffree(ns->pcopy);
+  ffree(ns->slab);
+  ffree(ns->ppart);
+  ns->pool = nullptr;
+  ns->pcount = nullptr;
+  ns->pok = nullptr;
+  ns->pcopy = ns->slab = ns->ppart = nullptr;
+  ns->slab_bytes = ns->ppart_bytes = 0;
+  ns->p_rn = 0;
+}
+
+// masters, counters and the open window's statistics to zero
+static hipError_t pool_clear(NutsState* ns, gm_dtype dt, int D) {
+  const size_t esz = dt == GM_F32 ? 4 : 8;
+  hipError_t e = hipMemset(ns->pool, 0, NutsState::pool_doubles(D) * sizeof(double));
+  if (e == hipSuccess) e = hipMemset(ns->pcount, 0, 4 * sizeof(long long));
+  if (e == hipSuccess) e = hipMemset(ns->pok, 0, sizeof(int));
+  if (e == hipSuccess) e = hipMemset(ns->pcopy, 0, 2 * (size_t)D * D * esz);
+  ns->p_rn = 0;
+  return e;
+}
+
+int nuts_set_convention(NutsState* ns, gm_dtype dt, long long C, int D, int convention, int pooled) {
+  const size_t esz = dt == GM_F32 ? 4 : 8;
+  const bool want_pool = convention == 1 && D >= 2 && D <= GM_DENSE_MAX_DIM;
+  // everything that can fail first: the sampler is unchanged on an error
+  void* scratch5 = nullptr;
+  if (convention == 1 && ns->mass_mode == 2 && !ns->convention) {  // one more [D][D] per chain (the precision)
+    if (hipMalloc(&scratch5, 5 * (size_t)C * D * D * esz) != hipSuccess) {
+      (void)hipGetLastError();
+      set_error("mass-matrix state allocation failed");
+      return GM_ENOMEM;
+    }
+  }
+  if (want_pool && !ns->pool) {
+    NutsState tmp;
+    hipError_t e = hipMalloc((void**)&tmp.pool, NutsState::pool_doubles(D) * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&tmp.pcount, 4 * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc((void**)&tmp.pok, sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&tmp.pcopy, 2 * (size_t)D * D * esz);
+    if (e == hipSuccess) e = pool_clear(&tmp, dt, D);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      pool_free(&tmp);
+      ffree(scratch5);
+      set_error(std::string("pooled-metric state allocation failed: ") + hipGetErrorString(e));
+      return GM_ENOMEM;
+    }
+    ns->pool = tmp.pool;
+    ns->pcount = tmp.pcount;
+    ns->pok = tmp.pok;
+    ns->pcopy = tmp.pcopy;
+  } else if (!want_pool) {
+    pool_free(ns);
+  }
+  if (scratch5) {
+    ffree(ns->mscratch);
+    ns->mscratch = scratch5;
+  }
+  ns->convention = convention;
+  ns->pooled = pooled;
+  return GM_OK;
+}
+
+int nuts_get_pooled(NutsState& ns, int D, double* sigma, double* chol_prec, long long* updates,
+                    long long* failed) {
+  const size_t dd = (size_t)D * D;
+  long long cnt[4] = {0, 0, 0, 0};
+  hipError_t e = hipMemcpy(cnt, ns.pcount, sizeof(cnt), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && sigma) e = hipMemcpy(sigma, ns.p_sig(), dd * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && chol_prec) e = hipMemcpy(chol_prec, ns.p_lp(D), dd * 8, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    set_error(std::string("pooled-metric copy failed: ") + hipGetErrorString(e));
+    return GM_EHIP;
+  }
+  if (updates) *updates = cnt[0];
+  if (failed) *failed = cnt[1];
+  return GM_OK;
+}
+
+int nuts_set_pooled_metric(NutsState& ns, gm_dtype dt, long long C, int D, const double* sigma, hipStream_t st) {
+  hipError_t e = hipMemcpyAsync(ns.p_in(D), sigma, (size_t)D * D * 8, hipMemcpyHostToDevice, st);
+  // factored by the kernel that factors an adapted metric; counters, window
+  // statistics and Welford state untouched, no epsilon re-find
+  if (e == hipSuccess)
+    e = dt == GM_F32 ? pooled_window_launch<float>(ns, C, D, 0, 0, 0, 0, st)
+                     : pooled_window_launch<double>(ns, C, D, 0, 0, 0, 0, st);
+  int ok = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&ok, ns.pok, sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    set_error(std::string("pooled-metric set failed: ") + hipGetErrorString(e));
+    return GM_EHIP;
+  }
+  if (!ok) {  // (nothing was written)
+    set_error("sigma is not positive definite in float64 (its inverse did not factor)");
+    return GM_EINVAL;
+  }
+  return GM_OK;
+}
+
 int nuts_set_mass(NutsState* ns, gm_dtype dt, long long C, int D, int mode, long long start_buffer,
                   long long end_buffer, long long initial_window, double regularize, double jitter) {
   mass_free(ns);
+  if (ns->pool && pool_clear(ns, dt, D) != hipSuccess) return GM_EHIP;
   if (mode == 0) return GM_OK;
   const size_t esz = dt == GM_F32 ? 4 : 8;
   const size_t cd = (size_t)C * D * esz, cdd = (size_t)C * D * D * esz;
@@ -382,7 +710,7 @@ int nuts_set_mass(NutsState* ns, gm_dtype dt, long long C, int D, int mode, long
     // into the padded columns of a D < 32 metric; nuts_device.h chol_global_cols)
     if (e == hipSuccess) e = hipMalloc(&ns->mchol, cdd + (size_t)D * esz);
     if (e == hipSuccess) e = hipMalloc(&ns->rm2, cdd);
-    if (e == hipSuccess) e = hipMalloc(&ns->mscratch, 4 * cdd);
+    if (e == hipSuccess) e = hipMalloc(&ns->mscratch, (4 + (ns->convention ? 1 : 0)) * cdd);
   }
   if (e != hipSuccess) {
     mass_free(ns);
@@ -439,6 +767,7 @@ void nuts_free_state(NutsState* ns) {
   ffree(ns->stk_vec);
   ffree(ns->n_leapfrog);
   ffree(ns->zbuf);
+  pool_free(ns);
   *ns = NutsState();
 }
 
@@ -467,6 +796,43 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
   // re-find (generic_nuts.rs:897-921). The window schedule depends on m and
   // n_discard only, so it is the same for every chain.
   const long long chunk = steps_per_launch;
+  // The pooled metric: a warm-up launch stores its window rows (the positions
+  // the per-chain Welford state takes, sb < m < lim) to a scratch slab
+  // through the launch's sample arguments; after the launch the pooled
+  // statistics take the slab's rows on the stream (pivot at the window's
+  // first row, Gram partials, their fixed-order reduction: hmc_dense_kernels.hip),
+  // and a window end replaces every chain's metric.
+  const bool pool_on = ns.pooled && ns.convention == 1 && ns.mass_mode && !step_mode && ns.pool != nullptr;
+  const long long plim = n_discard > ns.m_eb ? n_discard - ns.m_eb : 0;
+  const size_t row_bytes = (size_t)C * D * esz;
+  const long long slab_rows = std::max<long long>(1, (long long)((64u << 20) / row_bytes));
+  // gram row batches whose partials stay within 16 MiB
+  const long long gram_rb = std::max<long long>(1, (16LL << 20) / (long long)hmc_dense_gram_part_bytes(C, 1));
+  if (pool_on) {
+    const long long wrows = std::min(plim - 1, total) - ns.m_sb;  // window rows of this run
+    if (wrows > 0) {  // both scratch buffers once, before anything is enqueued
+      const long long rows = std::min(std::min(slab_rows, chunk), wrows);
+      const size_t need = (size_t)rows * row_bytes;
+      const size_t pneed = hmc_dense_gram_part_bytes(C, (int)std::min(gram_rb, rows));
+      if (need > ns.slab_bytes) {
+        ffree(ns.slab);
+        ns.slab = nullptr;
+        ns.slab_bytes = 0;
+        if (hipMalloc(&ns.slab, need) == hipSuccess) ns.slab_bytes = need;
+      }
+      if (pneed > ns.ppart_bytes) {
+        ffree(ns.ppart);
+        ns.ppart = nullptr;
+        ns.ppart_bytes = 0;
+        if (hipMalloc(&ns.ppart, pneed) == hipSuccess) ns.ppart_bytes = pneed;
+      }
+      if (!ns.slab || !ns.ppart) {
+        (void)hipGetLastError();
+        set_error("pooled-metric scratch allocation failed");
+        return GM_ENOMEM;
+      }
+    }
+  }
   std::vector<long long> seg_start, seg_len;
   std::vector<char> seg_update;
   {
@@ -487,6 +853,13 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
     do {
       long long n = total - s0 < chunk ? total - s0 : chunk;
       if (n < 0) n = 0;
+      if (pool_on) {  // window rows (sb < m < lim) go to the slab: no more than it holds, nothing after them
+        const long long first = (s0 + 1 > ns.m_sb + 1) ? s0 + 1 : ns.m_sb + 1;
+        if (first < plim && first <= s0 + n) {
+          if (n > first - 1 - s0 + slab_rows) n = first - 1 - s0 + slab_rows;
+          if (n > plim - 1 - s0) n = plim - 1 - s0;
+        }
+      }
       char upd = 0;
       if (wi < wends.size() && wends[wi] <= s0 + n) {  // cut at the window end (step m = s0 + n)
         n = wends[wi] - s0;
@@ -519,6 +892,10 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
     hipMemsetAsync(ns.rm2d, 0, (size_t)C * D * esz, st);
     if (ns.mass_mode == 2) hipMemsetAsync(ns.rm2, 0, (size_t)C * D * D * esz, st);
     hipMemsetAsync(ns.updated, 0, C * sizeof(int), st);
+    if (ns.pool) {  // and the pooled statistics with it
+      hipMemsetAsync(ns.p_c0(D), 0, (2 * (size_t)D + (size_t)D * D) * sizeof(double), st);
+      ns.p_rn = 0;
+    }
   }
   // The frozen-dense instantiation (MASS 3) for launches without a window
   // end or Welford collection when every chain's metric is dense: read the
@@ -583,6 +960,17 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
     a.t0 = start;
     a.row_shift = row_shift;
     a.n_rows = n_rows_total > 0 ? n_rows_total : 0;
+    long long used = 0;  // rows of this launch that enter the pooled statistics
+    if (pool_on) {  // transitions t = start + 1 .. start + nst with sb < t < lim
+      const long long first = std::max(start + 1, ns.m_sb + 1);
+      const long long hi = std::min(start + nst, plim - 1);
+      if (hi >= first) {  // (the segments were cut so that such a launch collects nothing and fits the slab)
+        used = hi - first + 1;
+        a.samples = ns.slab;
+        a.row_shift = first;
+        a.n_rows = used;
+      }
+    }
     if (ns.mass_mode) {
       a.mass_mode = ns.mass_mode;
       a.mkind = ns.mkind;
@@ -728,20 +1116,46 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
       set_error(std::string("NUTS launch failed: ") + hipGetErrorString(e));
       return GM_EHIP;
     }
+    if (used > 0) {  // the launch's window rows into s1 and S2, row after row (timed with the launch)
+      hipError_t e3 = hipSuccess;
+      if (ns.p_rn == 0) e3 = launch_hmc_dense_pivot(dt, ns.slab, C, D, ns.p_c0(D), st);
+      for (long long r = 0; r < used && e3 == hipSuccess; r += gram_rb) {
+        const int rows = (int)std::min(gram_rb, used - r);
+        e3 = launch_hmc_dense_gram(dt, (const char*)ns.slab + (size_t)r * row_bytes, rows, C, D, ns.p_c0(D),
+                                   (double*)ns.ppart, ns.p_s1(D), ns.p_S2(D), st);
+      }
+      if (e3 != hipSuccess) {
+        set_error(std::string("pooled statistics launch failed: ") + hipGetErrorString(e3));
+        return GM_EHIP;
+      }
+      ns.p_rn += used;
+    }
     hipEventRecord(evs[2 * li + 1], st);
     pending_refind = 0;
-    if (seg_update[li]) {  // maybe_update_mass_matrix for every chain
+    if (seg_update[li] && pool_on) {  // the pooled window end (fewer than 5 rows: nothing changes)
+      if (ns.p_rn >= 5) {
+        const hipError_t e2 = dt == GM_F32 ? pooled_window_launch<float>(ns, C, D, 1, ns.p_rn * C, 1, 1, st)
+                                           : pooled_window_launch<double>(ns, C, D, 1, ns.p_rn * C, 1, 1, st);
+        if (e2 != hipSuccess) {
+          set_error(std::string("pooled window launch failed: ") + hipGetErrorString(e2));
+          return GM_EHIP;
+        }
+        ns.p_rn = 0;
+        pending_refind = 1;
+        refind_step = *step + (uint64_t)(start + nst - 1);
+      }
+    } else if (seg_update[li]) {  // maybe_update_mass_matrix for every chain
       const unsigned blocks = (unsigned)((C + 63) / 64);
       if (dt == GM_F32)
         hipLaunchKernelGGL(nuts_mass_update_kernel<float>, dim3(blocks), dim3(64), 0, st, C, D, ns.mass_mode,
-                           ns.m_reg, ns.m_jit, ns.mkind, (float*)ns.dinv, (float*)ns.dsq, (float*)ns.minv,
-                           (float*)ns.mchol, ns.rn, (float*)ns.rmean, (float*)ns.rm2d, (float*)ns.rm2,
-                           ns.updated, (float*)ns.mscratch);
+                           ns.convention, ns.m_reg, ns.m_jit, ns.mkind, (float*)ns.dinv, (float*)ns.dsq,
+                           (float*)ns.minv, (float*)ns.mchol, ns.rn, (float*)ns.rmean, (float*)ns.rm2d,
+                           (float*)ns.rm2, ns.updated, (float*)ns.mscratch);
       else
         hipLaunchKernelGGL(nuts_mass_update_kernel<double>, dim3(blocks), dim3(64), 0, st, C, D, ns.mass_mode,
-                           ns.m_reg, ns.m_jit, ns.mkind, (double*)ns.dinv, (double*)ns.dsq, (double*)ns.minv,
-                           (double*)ns.mchol, ns.rn, (double*)ns.rmean, (double*)ns.rm2d, (double*)ns.rm2,
-                           ns.updated, (double*)ns.mscratch);
+                           ns.convention, ns.m_reg, ns.m_jit, ns.mkind, (double*)ns.dinv, (double*)ns.dsq,
+                           (double*)ns.minv, (double*)ns.mchol, ns.rn, (double*)ns.rmean, (double*)ns.rm2d,
+                           (double*)ns.rm2, ns.updated, (double*)ns.mscratch);
       hipError_t e2 = hipGetLastError();
       if (e2 != hipSuccess) {
         set_error(std::string("mass update launch failed: ") + hipGetErrorString(e2));

@@ -31,6 +31,16 @@ class NUTSMassMatrixConfig:
     regularize: float = 0.05
     jitter: float = 1e-6
     dense_max_dim: int = 75
+    # The metric convention (no reference counterpart beyond the default):
+    # "reference" is M = Sigma_hat, "whitening" is M^-1 = Sigma_hat (Stan's);
+    # pooled estimates one Sigma_hat from all chains (whitening only,
+    # 2 <= dim <= 64) instead of one per chain.
+    convention: str = "reference"
+    pooled: bool = False
+
+    @property
+    def convention_code(self) -> int:
+        return {"reference": 0, "whitening": 1}[self.convention.lower()]
 
     @classmethod
     def disabled(cls) -> "NUTSMassMatrixConfig":
@@ -72,9 +82,42 @@ class NUTS(Sampler):
         return s
 
     def set_mass_adaptation(self, cfg: NUTSMassMatrixConfig) -> "NUTS":
-        _lib.check(self._lib.gm_nuts_set_mass_adaptation(
+        # the convention first (it only checks its own arguments and the dim),
+        # put back if the adaptation itself is refused
+        before = getattr(self, "_convention", (0, 0))
+        conv = (cfg.convention_code, 1 if cfg.pooled else 0)
+        _lib.check(self._lib.gm_nuts_set_metric_convention(self._h, *conv))
+        rc = self._lib.gm_nuts_set_mass_adaptation(
             self._h, cfg.mode, cfg.start_buffer, cfg.end_buffer, cfg.initial_window, cfg.regularize,
-            cfg.jitter, cfg.dense_max_dim))
+            cfg.jitter, cfg.dense_max_dim)
+        if rc != _lib.GM_OK:  # (a call that succeeds leaves the refusal's message in place)
+            self._lib.gm_nuts_set_metric_convention(self._h, *before)
+        _lib.check(rc)
+        self._convention = conv
+        return self
+
+    def pooled_metric(self) -> tuple[np.ndarray, np.ndarray]:
+        """The pooled whitening metric's float64 masters: Sigma_hat (= M^-1)
+        and the lower Cholesky factor of its inverse, each [dim, dim]."""
+        d = (self.dim, self.dim)
+        sigma, lp = np.zeros(d), np.zeros(d)
+        _lib.check(self._lib.gm_nuts_get_pooled_metric(self._h, _lib.ptr(sigma), _lib.ptr(lp), None, None))
+        return sigma, lp
+
+    def metric_updates(self) -> tuple[int, int]:
+        """(updates, failed) of the pooled metric's window ends."""
+        u, f = C.c_int64(), C.c_int64()
+        _lib.check(self._lib.gm_nuts_get_pooled_metric(self._h, None, None, C.byref(u), C.byref(f)))
+        return int(u.value), int(f.value)
+
+    def set_pooled_metric(self, sigma) -> "NUTS":
+        """Sigma_hat (float64 [dim, dim], symmetric positive definite) as
+        every chain's dense whitening metric, e.g. one warmed up by a sampler
+        with fewer chains (gm_nuts_set_pooled_metric)."""
+        sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+        if sigma.shape != (self.dim, self.dim):
+            raise ValueError(f"sigma must be [{self.dim}, {self.dim}]")
+        _lib.check(self._lib.gm_nuts_set_pooled_metric(self._h, _lib.ptr(sigma)))
         return self
 
     def mass_matrix(self) -> MassMatrix:

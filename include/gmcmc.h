@@ -395,6 +395,38 @@ int gm_nuts_get_step_size(gm_sampler* s, double* eps, double* eps_bar);
 int gm_nuts_set_mass_adaptation(gm_sampler* s, int32_t mode, int64_t start_buffer, int64_t end_buffer,
                                 int64_t initial_window, double regularize, double jitter,
                                 int64_t dense_max_dim);
+/* The convention of the metric that the warm-up's window ends write, from
+ * the next window end on (no reference counterpart beyond the default).
+ * convention 0 (the default) is the reference's, M = Sigma_hat: the slots
+ * that gm_nuts_get_mass reads hold Sigma_hat^-1 (or 1/var) and
+ * chol(Sigma_hat) (or sqrt(var)). convention 1 is the whitening one,
+ * M^-1 = Sigma_hat (Stan's): the same slots hold Sigma_hat (or var) and
+ * chol(Sigma_hat^-1) (or 1/sqrt(var)), from the same statistics, floors and
+ * jitter tries; the sampling kernels are the same and take either as the
+ * same pair of operators. pooled 1 (whitening only, 2 <= dim <= 64, else
+ * GM_EINVAL) estimates one Sigma_hat in float64 from the window rows of all
+ * chains of the sampler instead of one per chain, n = rows * n_chains:
+ * Sigma_hat = (1 - regularize) S + regularize I, diagonal floored at
+ * max(jitter, 1e-10); a window of fewer than 5 rows changes nothing; a
+ * non-positive or non-finite pivot keeps the previous metric and is counted.
+ * Every chain's slots get the same matrices, rounded once to the sampler
+ * dtype. The setting survives gm_nuts_set_mass_adaptation. A failed call
+ * leaves the sampler as it was. */
+int gm_nuts_set_metric_convention(gm_sampler* s, int32_t convention, int32_t pooled);
+/* The pooled metric's float64 masters, Sigma_hat and the lower Cholesky
+ * factor of its inverse ([dim][dim] each), and the numbers of window ends
+ * that replaced the metric / kept it after a failed factorisation. Any output
+ * may be NULL. GM_ESTATE unless the whitening convention is set at
+ * 2 <= dim <= 64. */
+int gm_nuts_get_pooled_metric(gm_sampler* s, double* sigma, double* chol_prec, int64_t* updates,
+                              int64_t* failed);
+/* sigma (float64 [dim][dim]: finite, exactly symmetric, positive definite,
+ * else GM_EINVAL) as every chain's dense whitening metric, factored on the
+ * device as at a window end; e.g. a metric warmed up by a sampler with fewer
+ * chains. Needs mode 2 and the whitening convention (GM_ESTATE otherwise).
+ * Step sizes, counters and warm-up state are untouched. A failed call leaves
+ * the sampler as it was. */
+int gm_nuts_set_pooled_metric(gm_sampler* s, const double* sigma);
 /* The current metric: mode, per-chain kind [C] (0 identity, 1 diagonal,
  * 2 dense), diagonal inverse and sqrt [C][dim], dense inverse and Cholesky
  * factor [C][dim][dim] (mode 2). Any output may be NULL. */
