@@ -84,13 +84,20 @@ hipError_t launch_hmc_adapt_window(gm_dtype dt, long long C, int D, double regul
 constexpr int GM_DENSE_MAX_DIM = 64;
 hipError_t launch_hmc_dense(gm_dtype dt, const TargetDev& tg, const Layout& lay, const HmcDenseLaunch& a,
                             int mode, hipStream_t st, LaunchEvents ev = {});
-// pooled warm-up statistics of x [rows][C][D] in float64: the pivot c0 (mean
-// over chains of row 0), then s1 += sum (x - c0), S2 += sum (x - c0)(x - c0)^T
-// row after row; part: hmc_dense_gram_part_bytes(C, rows) bytes of scratch
-size_t hmc_dense_gram_part_bytes(long long C, int rows);
-hipError_t launch_hmc_dense_pivot(gm_dtype dt, const void* x, long long C, int D, double* c0, hipStream_t st);
-hipError_t launch_hmc_dense_gram(gm_dtype dt, const void* x, int rows, long long C, int D, const double* c0,
-                                 double* part, double* s1, double* S2, hipStream_t st);
+// Pooled warm-up statistics in float64 (HMC dense metric, NUTS pooled metric).
+// A warm-up launch stores its window rows to the slab [rows][C][D];
+// pooled_accumulate then takes slab rows [0, used): the pivot c0 (mean over
+// chains of row 0) when the window has no rows yet (*rn == 0), then
+// s1 += sum (x - c0), S2 += sum (x - c0)(x - c0)^T row after row, in batches
+// whose Gram partials fit `part` (gm_plan.h: gram_rows_for); *rn += used.
+struct PooledScratch {
+  void *slab = nullptr, *part = nullptr;
+  size_t slab_bytes = 0, part_bytes = 0;
+};
+// both buffers for launches of at most `rows` window rows (ensure_buf)
+int pooled_scratch_ensure(PooledScratch& ps, long long rows, long long C, int D, size_t esz);
+hipError_t pooled_accumulate(gm_dtype dt, const PooledScratch& ps, long long used, long long C, int D,
+                             long long* rn, double* c0, double* s1, double* S2, hipStream_t st);
 // Sigma (from the statistics, or sig_in), its Cholesky factor and A = L^-T,
 // float64 masters and sampler-dtype copies; statistics reset; restart of the
 // dual averaging (one workgroup)
@@ -158,6 +165,9 @@ int build_target(const gm_target* t, gm_dtype dt, long long dim, TargetDev* out,
                  void** d_prec);
 
 // ---- utilities -------------------------------------------------------------
+// A grow-only device buffer: at least `need` bytes behind *p (gmcmc_api.cpp);
+// GM_ENOMEM with the error text set when the allocation fails.
+int ensure_buf(void** p, size_t* cap, size_t need);
 // [rows][C][D] -> [C][rows][D]
 // dst = src in 16-byte words (both 16-byte aligned), util_kernels.hip
 hipError_t launch_copy16(const void* src, void* dst, long long words, hipStream_t st);

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "gm_internal.h"
+#include "gm_plan.h"
 
 namespace gm {
 
@@ -35,7 +36,7 @@ struct NutsState {
   int mass_mode = 0;          // 0 off (identity), 1 diagonal, 2 dense
   long long m_sb = 0, m_eb = 0;
   double m_reg = 0, m_jit = 0;
-  long long sched_next = 0, sched_len = 0;  // MassMatrixWarmup window schedule (persists)
+  WindowSchedule sched;       // MassMatrixWarmup window schedule (persists across runs)
   int* mkind = nullptr;       // [C] 0 identity, 1 diagonal, 2 dense
   void* dinv = nullptr;       // [C][D]
   void* dsq = nullptr;        // [C][D]
@@ -58,9 +59,7 @@ struct NutsState {
   int* pok = nullptr;          // the last window kernel's outcome
   void* pcopy = nullptr;       // the masters rounded to the sampler dtype, 2 [D][D]
   long long p_rn = 0;          // rows in the open window's pooled statistics
-  void* slab = nullptr;        // a warm-up launch's window rows [rows][C][D]
-  void* ppart = nullptr;       // Gram partials (hmc_dense_gram_part_bytes)
-  size_t slab_bytes = 0, ppart_bytes = 0;
+  PooledScratch ps;            // a warm-up launch's window rows [rows][C][D], Gram partials
   double* p_sig() const { return pool; }
   double* p_lp(int D) const { return pool + (size_t)D * D; }
   double* p_in(int D) const { return pool + 2 * (size_t)D * D; }

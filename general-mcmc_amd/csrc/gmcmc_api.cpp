@@ -1,5 +1,6 @@
 // gmcmc_api.cpp — the C ABI (include/gmcmc.h): sampler objects, device
-// memory, streams, run orchestration and error reporting.
+// memory, streams and error reporting; the run drivers behind gm_run* and
+// gm_step are in gmcmc_run.cpp.
 //
 // Orchestration mirrors the reference facades:
 //   HMC::new / run / run_positions      hmc.rs:113-181, batched_hmc.rs:62-123
@@ -26,8 +27,8 @@
 
 #include "gm_jit.h"
 #include "gm_layouts.h"
-#include "gm_nuts.h"
 #include "gm_rng.h"
+#include "gm_sampler.h"
 
 namespace gm {
 static thread_local std::string g_err;
@@ -118,25 +119,6 @@ Layout default_layout(int D, gm_dtype dt, int kind) {
 
 using namespace gm;
 
-#define GM_HIP(expr)                                                                   \
-  do {                                                                                 \
-    hipError_t _e = (expr);                                                            \
-    if (_e != hipSuccess) {                                                            \
-      set_error(std::string("HIP error ") + hipGetErrorString(_e) + " at " #expr);     \
-      return GM_EHIP;                                                                  \
-    }                                                                                  \
-  } while (0)
-
-#define GM_REQ(cond, msg)      \
-  do {                         \
-    if (!(cond)) {             \
-      set_error(msg);          \
-      return GM_EINVAL;        \
-    }                          \
-  } while (0)
-
-enum SamplerKind { K_HMC = 1, K_MH = 2, K_NUTS = 3 };
-
 // roctx ranges around the sampler entry points (the
 // reference times its runs with dev_tools::Timer, here the ranges appear in
 // rocprofv3 --marker-trace timelines). Enabled by GMCMC_ROCTX=1 (read once),
@@ -182,147 +164,7 @@ struct RoctxRange {
   }
 };
 
-// HMC with per-chain step sizes, a diagonal metric and their warm-up
-// (gm_hmc_set_*; hmc_adapt_device.h). `has`: the per-chain arrays exist and
-// the sampler runs hmc_adapt_kernel instead of hmc_kernel.
-struct HmcAdapt {
-  bool has = false;
-  int mode = 0;        // 0 none, 1 step size, 2 step size + diagonal metric
-  bool armed = false;  // the next run's n_discard transitions are the warm-up
-  double delta = 0.8;
-  long long sb = 0, eb = 0, iw = 0;
-  double reg = 0, jit = 0;
-  // dual-averaging restart counter and Welford count: the window schedule
-  // depends on the transition index only, so they are the same for every chain
-  long long k = 0, rn = 0;
-  long long pending_warm = 0;  // n_discard of the gm_run* call that is entering run_steps
-  void *eps = nullptr, *eps_bar = nullptr, *h_bar = nullptr, *mu = nullptr;       // [C]
-  void *dinv = nullptr, *dsq = nullptr, *rmean = nullptr, *rm2 = nullptr;         // [C][D]
-};
-
-// One dense metric shared by all chains (gm_hmc_set_dense_*;
-// hmc_dense_device.h). `on`: the sampler runs hmc_dense_kernel. The per-chain
-// step sizes, the dual-averaging state, the window configuration and the
-// counters k / rn (here: rows of pooled positions in the open window) are
-// HmcAdapt's, which a dense-metric sampler always has.
-struct HmcDense {
-  bool on = false;
-  double *minv = nullptr, *afac = nullptr;            // [D][D] float64 masters: Sigma, A = L^-T (row-major)
-  double *c0 = nullptr, *s1 = nullptr, *S2 = nullptr;  // pooled statistics: pivot [D], sums [D], [D][D]
-  double* sig_in = nullptr;                            // [D][D] staging of gm_hmc_set_dense_metric
-  void *minv_t = nullptr, *at_t = nullptr;             // sampler-dtype copies (at_t[j*D + i] = A_ij)
-  long long* counters = nullptr;                       // [2] metric updates, failed factorisations
-  void* slab = nullptr;                                // [rows][C][D] warm-up positions of one launch
-  size_t slab_bytes = 0;
-  void* part = nullptr;                                // gram partials
-  size_t part_bytes = 0;
-};
-// the slab's bound (GM_DENSE_MAX_DIM: gm_internal.h)
-constexpr size_t GM_DENSE_SLAB_BYTES = 64u << 20;
-
-// Per-transition sampler statistics (gm_sampler_set_stats; gm_launch.h
-// StatsRec). A run option: nothing of it enters a checkpoint.
-struct StatsRun {
-  int mode = 0;         // 0 off, 1 collected, 2 all
-  void* buf = nullptr;  // the last recording run's records [n][C]
-  size_t cap = 0;
-  bool active = false;  // a gm_run* call is recording (gm_step never does)
-  bool valid = false;   // the last run recorded: buf, n, first_collected and first_row are its
-  long long base = 0;   // run index of the first transition of the next run_steps call
-  long long first = 0;  // the run's first recorded transition
-  long long n = 0;      // transitions recorded
-  long long first_collected = 0, first_row = 0;
-  // a plain HMC sampler's recording launches: per-chain state of the creation
-  // step size and the identity metric for hmc_adapt_kernel's frozen mode
-  HmcAdapt ident;
-  void* scratch = nullptr;  // the reduction's scratch and outputs
-  size_t scratch_cap = 0;
-};
-
-struct gm_sampler {
-  int kind = 0;
-  gm_dtype dt = GM_F32;
-  size_t esz = 4;
-  long long C = 0;
-  int D = 0;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  TargetDev tg;
-  void* d_mu = nullptr;
-  void* d_prec = nullptr;
-  double eps = 0;
-  int L = 0;
-  double prop_std = 1;
-  double target_accept = 0.8;
-  int max_depth = 10;
-  uint64_t seed = 0;
-  uint64_t step = 0;
-  uint32_t chain_offset = 0;
-  void* d_q = nullptr;
-  void* d_logp = nullptr;
-  long long* d_acc = nullptr;
-  void* d_samples = nullptr;
-  size_t samples_bytes = 0;
-  void* d_tmp = nullptr;
-  size_t tmp_bytes = 0;
-  void* h_stage[2] = {nullptr, nullptr};  // pinned D2H staging slots (gm_copy_samples)
-  hipEvent_t stage_ev[2] = {nullptr, nullptr};
-  void* d_zs = nullptr;  // wide-layout HMC momentum scratch
-  size_t zs_bytes = 0;
-  Layout lay;
-  bool lay_from_wide = false;  // NUTS: a wide layout replaced for a dense metric (gm_nuts_set_mass_adaptation)
-  Layout lay_wide{};            // ... and that layout
-  long long steps_per_launch = 1000;
-  int lf_unroll = 0;  // HMC leapfrog-loop form: 0 by the wave count and L (hmc_lf_unroll), else 1, 2, 4, GM_LF_LONG or GM_LF_BLOCK
-  std::vector<hipEvent_t> evs;
-  double last_ms = 0;
-  long long last_launches = 0;
-  int last_unroll = 0;  // the leapfrog loop form of the last run's launches (gm_sampler_last_unroll)
-  bool last_ms_pending = false;  // HMC/MH: last_ms is read from evs[0..1] on request
-  bool async_runs = false;       // HMC/MH runs return after enqueueing (gm_sampler_set_async)
-  bool may_async = false;        // set by the entry points that honour async_runs
-  long long total_steps = 0;  // transitions since creation
-  long long last_rows = 0;    // sample rows produced by the last run
-  NutsState nuts;
-  HmcAdapt ha;
-  HmcDense hd;
-  StatsRun st;
-  // run_progress statistics: per-chain trackers (MH, NUTS) and a
-  // MultiChainTracker (HMC), one allocation each (TrackSet)
-  void* d_trk = nullptr;
-  size_t trk_bytes = 0;
-  unsigned long long trk_n = 0;  // ChainTracker steps taken (0: no stats yet)
-  void* d_mct = nullptr;
-  size_t mct_bytes = 0;
-};
-
-// Views into one tracker allocation: mean, msq, last [C*D]; p [C]; flags [C]
-// (int); rhat [D]; scalar [1].
-struct TrackSet {
-  float *mean, *msq, *last, *p, *rhat, *scalar;
-  int* flags;
-  static size_t bytes(long long C, int D) { return sizeof(float) * (3 * (size_t)C * D + 2 * C + D + 1); }
-  TrackSet(void* base, long long C, int D) {
-    float* f = (float*)base;
-    mean = f;
-    msq = f + (size_t)C * D;
-    last = f + 2 * (size_t)C * D;
-    p = f + 3 * (size_t)C * D;
-    flags = (int*)(p + C);
-    rhat = (float*)(flags + C);
-    scalar = rhat + D;
-  }
-  TrackLaunch launch() const {
-    TrackLaunch t;
-    t.mean = mean;
-    t.msq = msq;
-    t.last = last;
-    t.p = p;
-    return t;
-  }
-};
-
-static int ensure_buf(void** p, size_t* cap, size_t need) {
+int gm::ensure_buf(void** p, size_t* cap, size_t need) {
   if (*cap >= need) return GM_OK;
   if (*p) hipFree(*p);
   *p = nullptr;
@@ -403,7 +245,7 @@ static double hmc_eps_rounded(const gm_sampler* s) { return s->dt == GM_F32 ? (d
 // Allocates the per-chain arrays in their start state: every step size the
 // creation value, the identity metric, no statistics. From here on the sampler
 // runs hmc_adapt_kernel.
-static int hmc_adapt_ensure(gm_sampler* s, HmcAdapt& h) {
+int hmc_adapt_ensure(gm_sampler* s, HmcAdapt& h) {
   if (h.has) return GM_OK;
   if (s->tg.kind == GM_TARGET_CUSTOM) {  // a source that does not compile for this kernel fails here
     const int rc = jit_prepare(JIT_HMC_ADAPT0, s->dt, s->tg);
@@ -464,7 +306,7 @@ static int hmc_adapt_callable(gm_sampler* s) {
 static void hmc_dense_free(gm_sampler* s) {
   HmcDense& d = s->hd;
   for (void** p : {(void**)&d.minv, (void**)&d.afac, (void**)&d.c0, (void**)&d.s1, (void**)&d.S2,
-                   (void**)&d.sig_in, &d.minv_t, &d.at_t, (void**)&d.counters, &d.slab, &d.part}) {
+                   (void**)&d.sig_in, &d.minv_t, &d.at_t, (void**)&d.counters, &d.ps.slab, &d.ps.part}) {
     if (*p) hipFree(*p);
     *p = nullptr;
   }
@@ -978,502 +820,6 @@ int gm_sampler_last_run_stats(gm_sampler* s, double* kernel_ms, int64_t* launche
   if (kernel_ms) *kernel_ms = s->last_ms;
   if (launches) *launches = s->last_launches;
   return GM_OK;
-}
-
-// Leapfrog-loop unroll of the HMC kernel (identical results). Measured
-// (tools/probe_hmc_scaling.py): x4 is ~12% faster while the grid has at most
-// one wave per SIMD (latency bound), and 10-20% slower from two waves per
-// SIMD up.
-constexpr long long GM_LF_BLOCK_MIN_L1 = 2 * GM_LF_LONG;
-static int hmc_lf_unroll(long long waves, long long L, bool has_long, bool has_block) {
-  static const int simds = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-    return 4 * cus;
-  }();
-  // x4 at <= 1 wave per SIMD, x2 at <= 4 (the cfg2 headline), x1 above
-  // (cfg4's 8 and the north star's 16 waves per SIMD), measured per regime
-  const int form = waves <= simds ? 4 : waves <= 4 * simds ? 2 : 1;
-  // The long count-down form (GM_LF_LONG leapfrogs per trip) where x2 ran:
-  // above one and up to four waves per SIMD, in the kernels that compile it
-  // in (has_long), from the L at which its hot trips carry most of the steps.
-  if (form == 2 && has_long && L - 1 >= 2 * GM_LF_LONG) {
-    // The block form (passes of GM_LF_BLOCK straight-line leapfrogs) where
-    // the kernel has it, from the L at which it measured no slower than the
-    // long form (GM_LF_BLOCK_MIN_L1: L = 20 is 1.7 % faster, profiles/r11).
-    if (has_block && L - 1 >= GM_LF_BLOCK_MIN_L1) return GM_LF_BLOCK;
-    return GM_LF_LONG;
-  }
-  return form;
-}
-
-// hipSetDevice only when the calling thread is on another device (the call
-// is on every run's path). The current device is asked of the runtime
-// (a thread-local read in HIP), never cached here: gm_set_device and the
-// other entry points switch devices too.
-static hipError_t use_device(int dev) {
-  int cur = -1;
-  const hipError_t g = hipGetDevice(&cur);
-  if (g == hipSuccess && cur == dev) return hipSuccess;
-  return hipSetDevice(dev);
-}
-
-// One event pair per run (before the first launch, after the last): the
-// device time of the run's launches, read back after the run's stream
-// synchronize.
-static int ensure_run_events(gm_sampler* s) {
-  while (s->evs.size() < 2) {
-    hipEvent_t ev;
-    GM_HIP(hipEventCreate(&ev));
-    s->evs.push_back(ev);
-  }
-  return GM_OK;
-}
-
-// ---- per-transition sampler statistics (StatsRun) ---------------------------
-// The start of a recording run of `total` transitions, before anything is
-// launched: the record buffer (an allocation failure is a clean error) and,
-// for a plain HMC sampler, the identity per-chain state. fc: the first
-// transition whose resulting state is a collected row, first_row: that row.
-static int stats_begin(gm_sampler* s, long long total, long long fc, long long first_row) {
-  StatsRun& t = s->st;
-  t.active = false;
-  t.valid = false;
-  if (t.mode == 0) return GM_OK;
-  if (fc > total) fc = total;
-  const long long first = t.mode == 2 ? 0 : fc;
-  const long long n = total - first;
-  int rc = ensure_buf(&t.buf, &t.cap, (size_t)n * (size_t)s->C * 4 * s->esz);
-  if (!rc && s->kind == K_HMC && !s->ha.has) rc = hmc_adapt_ensure(s, t.ident);
-  if (rc) return rc;
-  t.base = 0;
-  t.first = first;
-  t.n = n;
-  t.first_collected = fc - first;
-  t.first_row = first_row;
-  t.valid = true;
-  t.active = n > 0;
-  return GM_OK;
-}
-// ends the recording when the run's entry point returns
-struct StatsScope {
-  gm_sampler* s;
-  ~StatsScope() { s->st.active = false; }
-};
-// the launch block of a launch whose first transition is `pos` of the current run_steps call
-static StatsLaunch stats_launch(const gm_sampler* s, long long pos) {
-  StatsLaunch t;
-  if (s->st.active) {
-    t.rec = s->st.buf;
-    t.t0 = s->st.base + pos;
-    t.first = s->st.first;
-    t.n = s->st.n;
-  }
-  return t;
-}
-
-// Runs `total` transitions; transitions with index >= collect_from (0-based
-// within this call) are stored at sample rows (index - collect_from).
-static int run_hmc_adapt(gm_sampler* s, long long total, long long collect_from, const StepHook* hook,
-                         long long chunk, int lf_unroll, long long warm);
-static int run_hmc_dense(gm_sampler* s, long long total, long long collect_from, const StepHook* hook,
-                         long long chunk, int lf_unroll, long long warm);
-
-static int run_steps(gm_sampler* s, long long total, long long collect_from, int progress,
-                     const TrackLaunch* trk = nullptr, const StepHook* hook = nullptr,
-                     long long chunk_override = 0) {
-  // the n_discard of a gm_run* call, consumed here: gm_step and the
-  // collection part of run_progress never start a warm-up
-  const long long pending_warm = s->ha.pending_warm;
-  s->ha.pending_warm = 0;
-  GM_HIP(use_device(s->device));
-  s->last_ms = 0;
-  s->last_launches = 0;
-  s->last_ms_pending = false;
-  // NUTS always launches: init_chain_state + row 0 even with zero transitions
-  if (total <= 0 && s->kind != K_NUTS) return GM_OK;
-  if (s->kind == K_NUTS) {
-    const StatsLaunch sl = stats_launch(s, 0);
-    int rc = nuts_run(s->nuts, s->dt, s->tg, s->lay, s->d_q, s->d_acc, s->d_samples, s->C, s->D,
-                      s->target_accept, s->seed, &s->step, s->chain_offset, total, collect_from,
-                      progress, chunk_override > 0 ? chunk_override : s->steps_per_launch,
-                      s->stream, s->evs, &s->last_ms, &s->last_launches, trk, hook, sl.rec ? &sl : nullptr);
-    return rc;
-  }
-  const long long chunk = chunk_override > 0 ? chunk_override : s->steps_per_launch;
-  const long long n_launch = (total + chunk - 1) / chunk;
-  int rc = ensure_run_events(s);
-  if (rc) return rc;
-  // (the long form is compiled into the plain kernel's one-chain-per-wave
-  // layouts with at most two elements per lane, hmc_part.inc, and the warm-up
-  // and dense-metric kernels run it as x1; chosen at one element per lane
-  // only: at two, 4096 chains x 128-D, it measured 3.5 % slower than x2,
-  // profiles/r10/ab_hmc_64x2_4096.log)
-  // (a recording run of a plain sampler goes through hmc_adapt_kernel's
-  // frozen mode with the identity state of StatsRun: the same bits)
-  const bool adapt_path = s->ha.has || s->st.active;
-  const bool has_long = !adapt_path && s->lay.lanes == 64 && s->lay.elems == 1;
-  // (the block form: hmc_part.inc, the targets with lf_block)
-  const bool has_block = has_long && s->tg.kind == GM_TARGET_ROSENBROCK;
-  const int lf_unroll = s->kind != K_HMC ? 1 : s->lf_unroll ? s->lf_unroll
-                                                             : hmc_lf_unroll((s->C * s->lay.lanes + 63) / 64, s->L, has_long, has_block);
-  s->last_unroll = lf_unroll;
-  if (s->kind == K_HMC && adapt_path) {
-    const long long warm = s->ha.armed && s->ha.mode ? std::min(pending_warm, total) : 0;
-    if (s->hd.on) return run_hmc_dense(s, total, collect_from, hook, chunk, lf_unroll, warm);
-    return run_hmc_adapt(s, total, collect_from, hook, chunk, lf_unroll, warm);
-  }
-  for (long long start = 0; start < total; start += chunk) {
-    LaunchEvents ev;  // start with the first launch, stop with the last
-    if (start == 0) ev.start = s->evs[0];
-    if (start + chunk >= total) ev.stop = s->evs[1];
-    const long long n = total - start < chunk ? total - start : chunk;
-    long long cf = collect_from - start;
-    if (cf < 0) cf = 0;
-    if (cf > n) cf = n;
-    long long row0 = start - collect_from;
-    if (row0 < 0) row0 = 0;
-    hipError_t e;
-    if (s->kind == K_HMC) {
-      HmcLaunch a;
-      a.q = s->d_q;
-      a.logp = s->d_logp;
-      a.accepts = s->d_acc;
-      a.samples = s->d_samples;
-      a.C = s->C;
-      a.D = s->D;
-      a.eps = s->eps;
-      a.L = s->L;
-      a.seed = s->seed;
-      a.step0 = s->step + start;
-      a.chain_offset = s->chain_offset;
-      a.n_steps = (int)n;
-      a.collect_from = (int)cf;
-      a.sample_row0 = row0;
-      a.lf_unroll = lf_unroll;
-      if (layout_is_wide(s->lay)) {
-        const size_t need = (size_t)s->C * (s->dt == GM_F32 ? 4 : 2) * s->lay.lanes * s->lay.elems * s->esz;
-        rc = ensure_buf(&s->d_zs, &s->zs_bytes, need);
-        if (rc) return rc;
-        a.zs = s->d_zs;
-      }
-      e = launch_hmc(s->dt, s->tg, s->lay, a, s->stream, ev);
-    } else {
-      MhLaunch a;
-      a.q = s->d_q;
-      a.logp = s->d_logp;
-      a.accepts = s->d_acc;
-      a.samples = s->d_samples;
-      a.C = s->C;
-      a.D = s->D;
-      a.prop_std = s->prop_std;
-      a.seed = s->seed;
-      a.step0 = s->step + start;
-      a.chain_offset = s->chain_offset;
-      a.n_steps = (int)n;
-      a.collect_from = (int)cf;
-      a.sample_row0 = row0;
-      if (trk) {
-        a.trk = *trk;
-        a.trk.n0 = trk->n0 + (unsigned long long)start;
-      }
-      e = launch_mh(s->dt, s->tg, s->lay, a, s->stream, ev);
-    }
-    if (e != hipSuccess) {
-      set_error(std::string("kernel launch failed: ") + hipGetErrorString(e));
-      return GM_EHIP;
-    }
-    if (hook && *hook) {
-      rc = (*hook)(start + n);
-      if (rc) return rc;
-    }
-  }
-  s->step += total;
-  s->total_steps += total;
-  if (!(s->async_runs && s->may_async)) GM_HIP(hipStreamSynchronize(s->stream));
-  s->last_ms_pending = true;
-  s->last_launches = n_launch;
-  return GM_OK;
-}
-
-// The metric windows' ends of an HMC warm-up of `warm` transitions, by
-// transition index m: the NUTS schedule (nuts_run / nuts_set_mass) over
-// sb < m < lim = warm - eb. One schedule for the diagonal (run_hmc_adapt,
-// mode 2) and the dense (run_hmc_dense) warm-up.
-static std::vector<long long> hmc_window_ends(const HmcAdapt& h, long long warm, long long lim) {
-  std::vector<long long> wends;
-  long long sched_len = h.iw > 10 ? h.iw : 10;
-  long long sched_next = (h.sb > 1 ? h.sb : 1) + sched_len;
-  for (long long m = 1; m <= warm; ++m) {
-    if (m <= h.sb || !(m < lim)) continue;
-    if (m >= sched_next || m + 1 >= lim) {
-      sched_next += sched_len;
-      sched_len = sched_len * 2 < 400 ? sched_len * 2 : 400;
-      wends.push_back(m);
-    }
-  }
-  return wends;
-}
-
-// The HMC run of a sampler with per-chain step sizes / metric: the first
-// `warm` transitions are the warm-up (MODE 1 or 2 launches, cut at every
-// window end, where hmc_adapt_window_kernel runs on the stream, and at the
-// warm-up's end, where eps = eps_bar), the rest frozen (MODE 0). Nothing here
-// waits for the device, so asynchronous runs stay asynchronous.
-static int run_hmc_adapt(gm_sampler* s, long long total, long long collect_from, const StepHook* hook,
-                         long long chunk, int lf_unroll, long long warm) {
-  HmcAdapt& h = s->ha.has ? s->ha : s->st.ident;
-  const long long lim = warm > h.eb ? warm - h.eb : 0;
-  std::vector<long long> wends;
-  if (h.mode == 2) wends = hmc_window_ends(h, warm, lim);
-  size_t wi = 0;
-  long long n_launch = 0;
-  for (long long pos = 0; pos < total;) {
-    long long n = total - pos < chunk ? total - pos : chunk;
-    const bool in_warm = pos < warm;
-    bool upd = false;
-    if (in_warm) {
-      if (n > warm - pos) n = warm - pos;
-      if (wi < wends.size() && wends[wi] <= pos + n) {  // cut at the window end (transition m = pos + n)
-        n = wends[wi] - pos;
-        upd = true;
-        ++wi;
-      }
-    }
-    LaunchEvents ev;
-    if (pos == 0) ev.start = s->evs[0];
-    if (pos + n >= total) ev.stop = s->evs[1];
-    long long cf = collect_from - pos;
-    if (cf < 0) cf = 0;
-    if (cf > n) cf = n;
-    long long row0 = pos - collect_from;
-    if (row0 < 0) row0 = 0;
-    HmcAdaptLaunch a;
-    a.h.q = s->d_q;
-    a.h.logp = s->d_logp;
-    a.h.accepts = s->d_acc;
-    a.h.samples = s->d_samples;
-    a.h.C = s->C;
-    a.h.D = s->D;
-    a.h.eps = s->eps;
-    a.h.L = s->L;
-    a.h.seed = s->seed;
-    a.h.step0 = s->step + pos;
-    a.h.chain_offset = s->chain_offset;
-    a.h.n_steps = (int)n;
-    a.h.collect_from = (int)cf;
-    a.h.sample_row0 = row0;
-    a.h.lf_unroll = lf_unroll;
-    a.eps = h.eps;
-    a.eps_bar = h.eps_bar;
-    a.h_bar = h.h_bar;
-    a.mu = h.mu;
-    a.dinv = h.dinv;
-    a.dsq = h.dsq;
-    a.rmean = h.rmean;
-    a.rm2 = h.rm2;
-    a.delta = h.delta;
-    a.k0 = h.k;
-    a.rn0 = h.rn;
-    a.m0 = pos;
-    a.sb = h.sb;
-    a.lim = lim;
-    a.stats = stats_launch(s, pos);
-    hipError_t e = launch_hmc_adapt(s->dt, s->tg, s->lay, a, in_warm ? h.mode : 0, s->stream, ev);
-    if (e == hipSuccess && in_warm) {
-      h.k += n;
-      if (h.mode == 2) {  // transitions m in (pos, pos + n] with sb < m < lim
-        const long long lo = std::max(pos + 1, h.sb + 1), hi = std::min(pos + n, lim - 1);
-        if (hi >= lo) h.rn += hi - lo + 1;
-      }
-      if (upd && h.rn >= 5) {  // (fewer than 5 positions: nothing changes, the statistics are kept)
-        e = launch_hmc_adapt_window(s->dt, s->C, s->D, h.reg, h.jit, h.rn, h.eps, h.eps_bar, h.h_bar, h.mu,
-                                    h.dinv, h.dsq, h.rmean, h.rm2, s->stream);
-        h.k = 0;
-        h.rn = 0;
-      }
-      if (e == hipSuccess && pos + n == warm) {  // the warm-up is over: eps = eps_bar, frozen from here on
-        e = hipMemcpyAsync(h.eps, h.eps_bar, (size_t)s->C * s->esz, hipMemcpyDeviceToDevice, s->stream);
-        h.armed = false;
-      }
-    }
-    if (e != hipSuccess) {
-      set_error(std::string("kernel launch failed: ") + hipGetErrorString(e));
-      return GM_EHIP;
-    }
-    ++n_launch;
-    if (hook && *hook) {
-      const int rc = (*hook)(pos + n);
-      if (rc) return rc;
-    }
-    pos += n;
-  }
-  s->step += total;
-  s->total_steps += total;
-  if (!(s->async_runs && s->may_async)) GM_HIP(hipStreamSynchronize(s->stream));
-  s->last_ms_pending = true;
-  s->last_launches = n_launch;
-  return GM_OK;
-}
-
-// The HMC run of a dense-metric sampler: as run_hmc_adapt, with MODE 1
-// launches during the warm-up. While a window is open (sb < m < lim) the
-// launch stores its post-accept positions to the scratch slab through the
-// sample-store path (a warm-up launch collects nothing else), bounded by the
-// slab; after it the pooled statistics take the slab's rows on the stream
-// (pivot at the window's first row, then Gram partials and their fixed-order
-// reduction), and at a window end hmc_dense_window_kernel replaces the metric.
-// Nothing here waits for the device.
-static int run_hmc_dense(gm_sampler* s, long long total, long long collect_from, const StepHook* hook,
-                         long long chunk, int lf_unroll, long long warm) {
-  HmcAdapt& h = s->ha;
-  HmcDense& d = s->hd;
-  const long long lim = warm > h.eb ? warm - h.eb : 0;
-  const std::vector<long long> wends = hmc_window_ends(h, warm, lim);
-  const size_t row_bytes = (size_t)s->C * s->D * s->esz;
-  const long long slab_rows = std::max<long long>(1, (long long)(GM_DENSE_SLAB_BYTES / row_bytes));
-  // gram row batches whose partials stay within 16 MiB
-  const long long rb = std::max<long long>(1, (16LL << 20) / (long long)hmc_dense_gram_part_bytes(s->C, 1));
-  if (warm > 0 && lim - 1 > h.sb) {  // both scratch buffers once, before anything is enqueued
-    const long long rows = std::min(std::min(slab_rows, chunk), lim - 1 - h.sb);
-    int rc = ensure_buf(&d.slab, &d.slab_bytes, (size_t)rows * row_bytes);
-    if (!rc) rc = ensure_buf(&d.part, &d.part_bytes, hmc_dense_gram_part_bytes(s->C, (int)std::min(rb, rows)));
-    if (rc) return rc;
-  }
-  size_t wi = 0;
-  long long n_launch = 0;
-  for (long long pos = 0; pos < total;) {
-    long long n = total - pos < chunk ? total - pos : chunk;
-    const bool in_warm = pos < warm;
-    bool upd = false;
-    long long cf = collect_from - pos;
-    if (cf < 0) cf = 0;
-    if (cf > n) cf = n;
-    long long row0 = pos - collect_from;
-    if (row0 < 0) row0 = 0;
-    long long used = 0;  // rows of this launch that enter the pooled statistics
-    if (in_warm) {
-      if (n > warm - pos) n = warm - pos;
-      // transitions m = pos + s + 1 with sb < m < lim are stored from s = cf
-      const long long first = std::max(pos + 1, h.sb + 1);
-      if (first < lim && first <= pos + n) {
-        cf = first - pos - 1;
-        if (n > cf + slab_rows) n = cf + slab_rows;
-        if (n > lim - 1 - pos) n = lim - 1 - pos;  // nothing past the last window is stored
-      } else {
-        cf = n;
-      }
-      if (wi < wends.size() && wends[wi] <= pos + n) {  // cut at the window end (transition m = pos + n)
-        n = wends[wi] - pos;
-        upd = true;
-        ++wi;
-      }
-      if (cf > n) cf = n;
-      row0 = 0;
-      const long long hi = std::min(pos + n, lim - 1);
-      used = hi >= first ? hi - first + 1 : 0;
-    }
-    LaunchEvents ev;
-    if (pos == 0) ev.start = s->evs[0];
-    if (pos + n >= total) ev.stop = s->evs[1];
-    HmcDenseLaunch a;
-    a.h.q = s->d_q;
-    a.h.logp = s->d_logp;
-    a.h.accepts = s->d_acc;
-    a.h.samples = in_warm ? d.slab : s->d_samples;
-    a.h.C = s->C;
-    a.h.D = s->D;
-    a.h.eps = s->eps;
-    a.h.L = s->L;
-    a.h.seed = s->seed;
-    a.h.step0 = s->step + pos;
-    a.h.chain_offset = s->chain_offset;
-    a.h.n_steps = (int)n;
-    a.h.collect_from = (int)cf;
-    a.h.sample_row0 = row0;
-    a.h.lf_unroll = lf_unroll;
-    a.eps = h.eps;
-    a.eps_bar = h.eps_bar;
-    a.h_bar = h.h_bar;
-    a.mu = h.mu;
-    a.minv = d.minv_t;
-    a.at = d.at_t;
-    a.delta = h.delta;
-    a.k0 = h.k;
-    a.stats = stats_launch(s, pos);
-    // the run's stop event goes after the statistics when this launch has some
-    LaunchEvents kev = ev;
-    if (in_warm) kev.stop = nullptr;
-    hipError_t e = launch_hmc_dense(s->dt, s->tg, s->lay, a, in_warm ? 1 : 0, s->stream, kev);
-    if (e == hipSuccess && in_warm) {
-      h.k += n;
-      if (used > 0) {
-        if (h.rn == 0) e = launch_hmc_dense_pivot(s->dt, d.slab, s->C, s->D, d.c0, s->stream);
-        for (long long r = 0; r < used && e == hipSuccess; r += rb) {
-          const int rows = (int)std::min(rb, used - r);
-          e = launch_hmc_dense_gram(s->dt, (const char*)d.slab + (size_t)r * row_bytes, rows, s->C, s->D, d.c0,
-                                    (double*)d.part, d.s1, d.S2, s->stream);
-        }
-        h.rn += used;
-      }
-      if (e == hipSuccess && upd && h.rn >= 5) {  // (fewer than 5 rows: nothing changes, the statistics are kept)
-        e = launch_hmc_dense_window(s->dt, s->D, s->C, 1, h.rn * s->C, h.reg, h.jit, d.s1, d.S2, d.sig_in, d.minv,
-                                    d.afac, d.minv_t, d.at_t, d.counters, 1, 1, h.eps, h.eps_bar, h.h_bar, h.mu,
-                                    s->stream);
-        h.k = 0;
-        h.rn = 0;
-      }
-      if (e == hipSuccess && pos + n == warm) {  // the warm-up is over: eps = eps_bar, frozen from here on
-        e = hipMemcpyAsync(h.eps, h.eps_bar, (size_t)s->C * s->esz, hipMemcpyDeviceToDevice, s->stream);
-        h.armed = false;
-      }
-      if (e == hipSuccess && ev.stop) e = hipEventRecord(ev.stop, s->stream);
-    }
-    if (e != hipSuccess) {
-      set_error(std::string("kernel launch failed: ") + hipGetErrorString(e));
-      return GM_EHIP;
-    }
-    ++n_launch;
-    if (hook && *hook) {
-      const int rc = (*hook)(pos + n);
-      if (rc) return rc;
-    }
-    pos += n;
-  }
-  s->step += total;
-  s->total_steps += total;
-  if (!(s->async_runs && s->may_async)) GM_HIP(hipStreamSynchronize(s->stream));
-  s->last_ms_pending = true;
-  s->last_launches = n_launch;
-  return GM_OK;
-}
-
-static int run_impl(gm_sampler* s, int64_t n_collect, int64_t n_discard, int progress) {
-  GM_REQ(s, "sampler is NULL");
-  s->last_rows = n_collect;
-  GM_REQ(n_collect >= 0 && n_discard >= 0, "n_collect and n_discard must be >= 0");
-  GM_HIP(use_device(s->device));
-  int rc = ensure_buf(&s->d_samples, &s->samples_bytes, (size_t)n_collect * s->C * s->D * s->esz);
-  if (rc) return rc;
-  long long total = n_discard + n_collect;
-  s->ha.pending_warm = n_discard;
-  s->st.valid = false;
-  StatsScope scope{s};
-  if (s->kind == K_NUTS && !progress) {
-    // NUTS::run performs n_collect + n_discard - 1 transitions (nuts.rs:232-257);
-    // row r is the state after n_discard + r of them.
-    if (n_collect == 0) return GM_OK;
-    total = n_discard + n_collect - 1;
-    // (transition t ends in row t + 1 - n_discard; row 0 of a run without burn-in is the start state)
-    rc = stats_begin(s, total, n_discard > 0 ? n_discard - 1 : 0, n_discard > 0 ? 0 : 1);
-    if (rc) return rc;
-    return run_steps(s, total, n_discard, progress ? 1 : 0);
-  }
-  rc = stats_begin(s, total, n_discard, 0);
-  if (rc) return rc;
-  return run_steps(s, total, n_discard, progress ? 1 : 0);
 }
 
 int gm_run_device(gm_sampler* s, int64_t n_collect, int64_t n_discard, const void** dev_samples) {
@@ -2126,7 +1472,7 @@ int gm_hmc_set_dense_adaptation(gm_sampler* s, double target_accept, int64_t sta
   GM_HIP(hipMemset(d.c0, 0, D * 8));
   GM_HIP(hipMemset(d.s1, 0, D * 8));
   GM_HIP(hipMemset(d.S2, 0, D * D * 8));
-  h.mode = 1;  // the kernel's MODE while warming up; the windows are run_hmc_dense's
+  h.mode = 1;  // the kernel's MODE while warming up; the windows are launch_dense_seg's (gmcmc_run.cpp)
   h.armed = true;
   h.delta = target_accept;
   h.sb = start_buffer;
@@ -2521,8 +1867,8 @@ int gm_state_save(gm_sampler* s, void* out, uint64_t bytes) {
       GM_HIP(hipMemcpy(n.pcount + 2, &n.p_rn, sizeof(long long), hipMemcpyHostToDevice));
     h.m_sb = n.m_sb;
     h.m_eb = n.m_eb;
-    h.sched_next = n.sched_next;
-    h.sched_len = n.sched_len;
+    h.sched_next = n.sched.next;
+    h.sched_len = n.sched.len;
     h.m_reg = n.m_reg;
     h.m_jit = n.m_jit;
     h.nuts_m = n.m;
@@ -2630,8 +1976,8 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
   s->step = h.step;
   s->total_steps = h.total_steps;
   if (s->kind == K_NUTS) {
-    s->nuts.sched_next = h.sched_next;
-    s->nuts.sched_len = h.sched_len;
+    s->nuts.sched.next = h.sched_next;
+    s->nuts.sched.len = h.sched_len;
     s->nuts.m = h.nuts_m;
     s->nuts.n_discard = h.nuts_n_discard;
     if (s->nuts.pool)

@@ -14,7 +14,10 @@
 // The partition over chains depends on C only and the rows are added one
 // after another, so the sums do not depend on how the run was cut into
 // launches. No floating-point atomics.
+#include <algorithm>
+
 #include "gm_jit.h"
+#include "gm_plan.h"
 #include "gm_rng.h"
 
 namespace gm {
@@ -172,12 +175,13 @@ __global__ void hmc_dense_gram_reduce_kernel(const double* __restrict__ part, in
   *dst = a;
 }
 
-int hmc_dense_gram_blocks(long long C) { return (int)((C + GD_CB - 1) / GD_CB); }
-size_t hmc_dense_gram_part_bytes(long long C, int rows) {
+static int hmc_dense_gram_blocks(long long C) { return (int)((C + GD_CB - 1) / GD_CB); }
+static size_t hmc_dense_gram_part_bytes(long long C, int rows) {
   return (size_t)rows * hmc_dense_gram_blocks(C) * GD_PE * sizeof(double);
 }
 
-hipError_t launch_hmc_dense_pivot(gm_dtype dt, const void* x, long long C, int D, double* c0, hipStream_t st) {
+static hipError_t launch_hmc_dense_pivot(gm_dtype dt, const void* x, long long C, int D, double* c0,
+                                         hipStream_t st) {
   if (dt == GM_F32) hipLaunchKernelGGL(hmc_dense_pivot_kernel<float>, dim3(1), dim3(256), 0, st, (const float*)x, C, D, c0);
   else hipLaunchKernelGGL(hmc_dense_pivot_kernel<double>, dim3(1), dim3(256), 0, st, (const double*)x, C, D, c0);
   return hipGetLastError();
@@ -185,8 +189,8 @@ hipError_t launch_hmc_dense_pivot(gm_dtype dt, const void* x, long long C, int D
 
 // adds rows [0, rows) of x [rows][C][D] into s1 and S2; part holds
 // hmc_dense_gram_part_bytes(C, rows) bytes
-hipError_t launch_hmc_dense_gram(gm_dtype dt, const void* x, int rows, long long C, int D, const double* c0,
-                                 double* part, double* s1, double* S2, hipStream_t st) {
+static hipError_t launch_hmc_dense_gram(gm_dtype dt, const void* x, int rows, long long C, int D, const double* c0,
+                                        double* part, double* s1, double* S2, hipStream_t st) {
   const int nb = hmc_dense_gram_blocks(C);
   const dim3 grid((unsigned)nb, (unsigned)rows);
   if (dt == GM_F32)
@@ -199,6 +203,28 @@ hipError_t launch_hmc_dense_gram(gm_dtype dt, const void* x, int rows, long long
   hipLaunchKernelGGL(hmc_dense_gram_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const double*)part,
                      rows, nb, D, s1, S2);
   return hipGetLastError();
+}
+
+int pooled_scratch_ensure(PooledScratch& ps, long long rows, long long C, int D, size_t esz) {
+  const long long rb = gram_rows_for(hmc_dense_gram_part_bytes(C, 1));
+  int rc = ensure_buf(&ps.slab, &ps.slab_bytes, (size_t)rows * (size_t)C * D * esz);
+  if (!rc) rc = ensure_buf(&ps.part, &ps.part_bytes, hmc_dense_gram_part_bytes(C, (int)std::min(rb, rows)));
+  return rc;
+}
+
+hipError_t pooled_accumulate(gm_dtype dt, const PooledScratch& ps, long long used, long long C, int D,
+                             long long* rn, double* c0, double* s1, double* S2, hipStream_t st) {
+  const size_t row_bytes = (size_t)C * D * (dt == GM_F32 ? 4 : 8);
+  const long long rb = gram_rows_for(hmc_dense_gram_part_bytes(C, 1));
+  hipError_t e = hipSuccess;
+  if (*rn == 0) e = launch_hmc_dense_pivot(dt, ps.slab, C, D, c0, st);
+  for (long long r = 0; r < used && e == hipSuccess; r += rb) {
+    const int rows = (int)std::min(rb, used - r);
+    e = launch_hmc_dense_gram(dt, (const char*)ps.slab + (size_t)r * row_bytes, rows, C, D, c0, (double*)ps.part, s1,
+                              S2, st);
+  }
+  *rn += used;
+  return e;
 }
 
 // ---- window end / metric set --------------------------------------------------

@@ -590,13 +590,13 @@ static void pool_free(NutsState* ns) {
   ffree(ns->pcount);
   ffree(ns->pok);
   ffree(ns->pcopy);
-  ffree(ns->slab);
-  ffree(ns->ppart);
+  ffree(ns->ps.slab);
+  ffree(ns->ps.part);
   ns->pool = nullptr;
   ns->pcount = nullptr;
   ns->pok = nullptr;
-  ns->pcopy = ns->slab = ns->ppart = nullptr;
-  ns->slab_bytes = ns->ppart_bytes = 0;
+  ns->pcopy = nullptr;
+  ns->ps = PooledScratch();
   ns->p_rn = 0;
 }
 
@@ -730,8 +730,7 @@ int nuts_set_mass(NutsState* ns, gm_dtype dt, long long C, int D, int mode, long
   ns->m_reg = regularize;
   ns->m_jit = jitter;
   // MassMatrixWarmup::new (generic_nuts.rs:141-151)
-  ns->sched_len = initial_window > 10 ? initial_window : 10;
-  ns->sched_next = (start_buffer > 1 ? start_buffer : 1) + ns->sched_len;
+  ns->sched = WindowSchedule(start_buffer, initial_window);
   return hipDeviceSynchronize() == hipSuccess ? GM_OK : GM_EHIP;
 }
 
@@ -771,6 +770,207 @@ void nuts_free_state(NutsState* ns) {
   *ns = NutsState();
 }
 
+// The frozen-dense instantiation (MASS 3) for launches without a window
+// end or Welford collection when every chain's metric is dense: read the
+// chains' kinds back once (after the stream's earlier work)
+static int nuts_all_dense(NutsState& ns, const TargetDev& tg, const Layout& lay, const std::vector<Segment>& segs,
+                          long long C, hipStream_t st, bool* all_dense) {
+  bool any_update = false;
+  for (const Segment& g : segs) any_update = any_update || g.update;
+  if (ns.mass_mode == 2 && !any_update && tg.kind != GM_TARGET_CUSTOM && lay.lanes == 16 && lay.elems == 2) {
+    std::vector<int> kinds((size_t)C);
+    if (hipMemcpyAsync(kinds.data(), ns.mkind, C * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+      set_error("copy of the NUTS metric kinds failed");
+      return GM_EHIP;
+    }
+    *all_dense = C > 0;
+    for (int k : kinds) *all_dense = *all_dense && k == 2;
+  }
+  return GM_OK;
+}
+
+// The LDS budget of the run's launches (nuts_size_lds).
+static NutsLdsBudget nuts_lds_budget(const NutsState& ns) {
+  NutsLdsBudget budget;
+  budget.lds_cap = ns.lds_levels_cap;  // gm_nuts_set_lds_levels (-1: as many as fit)
+  // dense M^-1 resident in LDS (layout 16 x 2) when it fits: full matrices
+  // or packed lower triangles (nuts_size_lds); gm_nuts_set_dense_forms picks
+  // packed only or global memory (identical results)
+  budget.minv_lds = ns.dense_minv_lds;
+  budget.chol_lds = ns.dense_chol_lds;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&budget.ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      budget.ncu < 1)
+    budget.ncu = 256;
+  if (hipDeviceGetAttribute(&budget.lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
+      budget.lds_max < 1)
+    budget.lds_max = 64 * 1024;
+  return budget;
+}
+
+// The metric arguments of a launch while a metric is adapted or in use; the
+// dense metric's transposes are made on the stream ahead of the launch.
+static void nuts_mass_args(NutsState& ns, gm_dtype dt, long long C, int D, int pending_refind, uint64_t refind_step,
+                           bool all_dense, NutsRecLaunch& a, hipStream_t st) {
+  const long long nst = a.n_steps;
+  a.mass_mode = ns.mass_mode;
+  a.mkind = ns.mkind;
+  a.dinv = ns.dinv;
+  a.dsq = ns.dsq;
+  a.minv = ns.minv;
+  a.mchol = ns.mchol;
+  a.mchol_rm = ns.mchol;
+  if (ns.mass_mode == 2) {  // the transposes, in the update kernel's scratch (free between its launches)
+    const size_t esz = dt == GM_F32 ? 4 : 8, cdd = (size_t)C * D * D * esz;
+    void* mT = ns.mscratch;
+    void* lT = (char*)ns.mscratch + cdd;
+    const long long n = C * (long long)D * D;
+    const unsigned tb = (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+    if (dt == GM_F32) {
+      hipLaunchKernelGGL(mat_transpose_kernel<float>, dim3(tb), dim3(256), 0, st, C, D, (const float*)ns.minv,
+                         (float*)mT);
+      hipLaunchKernelGGL(mat_transpose_kernel<float>, dim3(tb), dim3(256), 0, st, C, D,
+                         (const float*)ns.mchol, (float*)lT);
+    } else {
+      hipLaunchKernelGGL(mat_transpose_kernel<double>, dim3(tb), dim3(256), 0, st, C, D,
+                         (const double*)ns.minv, (double*)mT);
+      hipLaunchKernelGGL(mat_transpose_kernel<double>, dim3(tb), dim3(256), 0, st, C, D,
+                         (const double*)ns.mchol, (double*)lT);
+    }
+    a.minv = mT;
+    a.mchol = lT;
+  }
+  a.rn = ns.rn;
+  a.rmean = ns.rmean;
+  a.rm2d = ns.rm2d;
+  a.rm2 = ns.rm2;
+  a.updated = ns.updated;
+  a.sb = ns.m_sb;
+  a.eb = ns.m_eb;
+  a.do_refind = pending_refind;
+  a.refind_step = refind_step;
+  // no Welford collection in the launch: every m >= lim or m <= start_buffer
+  const long long lim = ns.n_discard > ns.m_eb ? ns.n_discard - ns.m_eb : 0;
+  a.dense_frozen = (all_dense && !a.do_refind && (a.m0 + 1 >= lim || a.m0 + nst <= ns.m_sb)) ? 1 : 0;
+}
+
+// the launch's momenta in one parallel pass ahead of the tree kernel
+// (same values; skipped past GM_NUTS_ZBUF_MAX bytes, the kernel then draws
+// them itself), timed with the launch
+static void nuts_momentum_pass(NutsState& ns, gm_dtype dt, long long C, int D, uint64_t seed, uint32_t chain_offset,
+                               NutsRecLaunch& a, hipStream_t st) {
+  const size_t esz = dt == GM_F32 ? 4 : 8;
+  const long long nst = a.n_steps;
+  // [nst][C][D] momenta, then the start records [nst][C] (16-byte aligned)
+  const size_t nsc = (size_t)(nst > 0 ? nst : 0) * (size_t)C;
+  const size_t zmb = (nsc * (size_t)D * esz + 15) / 16 * 16;
+  const size_t zrb = nsc * (dt == GM_F32 ? sizeof(NutsStartRec<float>) : sizeof(NutsStartRec<double>));
+  // a frozen-dense launch (the MASS 3 kernel, 16 x 2): the metric applied
+  // in the pass as well, M^-1 p0 [nst][C][D] after the records
+  // (the frozen kernel is built for this pass, GM_DENSE_PREP: a launch the
+  // pass cannot serve -- pass off, buffer past its cap or not allocated --
+  // takes the adaptive dense kernel instead, the same bits)
+  const size_t dpl = (a.mass_mode == 2 && a.dense_frozen) ? nuts_dense_prep_lds(D, esz) : 0;
+  const size_t zvo = (zmb + zrb + 15) / 16 * 16;
+  if (GM_DENSE_PREP && a.dense_frozen &&
+      !(dpl > 0 && C <= 0x7fffffff && ns.momentum_pass && zvo + zmb <= (size_t)GM_NUTS_ZBUF_MAX))
+    a.dense_frozen = 0;
+  const bool dprep = GM_DENSE_PREP && a.dense_frozen;
+  const size_t zb = dprep ? zvo + zmb : zmb + zrb;
+  if (ns.momentum_pass && zb > 0 && zb <= (size_t)GM_NUTS_ZBUF_MAX) {
+    if (zb > ns.zbuf_bytes) {
+      if (ns.zbuf) hipFree(ns.zbuf);
+      ns.zbuf = nullptr;
+      ns.zbuf_bytes = 0;
+      // at most a quarter of the device memory free now: the buffer is
+      // kept for the sampler's later launches (gm_nuts_set_momentum_pass(s,
+      // 0) releases it), and must not crowd out other samplers' or the
+      // caller's allocations; without it the kernel draws its momenta
+      size_t fr = 0, tot = 0;
+      if (hipMemGetInfo(&fr, &tot) == hipSuccess && zb <= fr / 4 && hipMalloc(&ns.zbuf, zb) == hipSuccess)
+        ns.zbuf_bytes = zb;
+      else
+        (void)hipGetLastError();
+    }
+    if (ns.zbuf) {
+      const long long S = dt == GM_F32 ? 4 : 2;
+      const long long nb = (long long)((a.step0 + (uint64_t)nst - 1) / S - a.step0 / S + 1);
+      const long long work = nb * C * D;
+      const unsigned zbk = (unsigned)((work + 255) / 256 < 65536 ? (work + 255) / 256 : 65536);
+      void* zr = (char*)ns.zbuf + zmb;
+      const unsigned sbk = (unsigned)((nsc + 255) / 256 < 65536 ? (nsc + 255) / 256 : 65536);
+      // (the frozen-dense kernel draws its starts itself: GM_SREC_DENSE)
+      const bool recs = !(a.mass_mode == 2 && a.dense_frozen && !GM_SREC_DENSE);
+      if (dt == GM_F32) {
+        hipLaunchKernelGGL(nuts_momenta_kernel<float>, dim3(zbk), dim3(256), 0, st, seed, chain_offset, a.step0,
+                           nst, C, D, (float*)ns.zbuf);
+        if (recs)
+          hipLaunchKernelGGL(nuts_starts_kernel<float>, dim3(sbk), dim3(256), 0, st, seed, chain_offset, a.step0,
+                             nst, C, ns.max_depth, (NutsStartRec<float>*)zr);
+      } else {
+        hipLaunchKernelGGL(nuts_momenta_kernel<double>, dim3(zbk), dim3(256), 0, st, seed, chain_offset,
+                           a.step0, nst, C, D, (double*)ns.zbuf);
+        if (recs)
+          hipLaunchKernelGGL(nuts_starts_kernel<double>, dim3(sbk), dim3(256), 0, st, seed, chain_offset,
+                             a.step0, nst, C, ns.max_depth, (NutsStartRec<double>*)zr);
+      }
+      if (dprep) {  // p0 = L z in place of z, M^-1 p0 at zvo
+        void* pv = (char*)ns.zbuf + zvo;
+        if (dt == GM_F32)
+          hipLaunchKernelGGL(nuts_dense_momenta_kernel<float>, dim3((unsigned)C), dim3(DPREP_THREADS), dpl, st, nst, C, D,
+                             (const float*)a.mchol_rm, (const float*)a.minv, (float*)ns.zbuf, (float*)pv);
+        else
+          hipLaunchKernelGGL(nuts_dense_momenta_kernel<double>, dim3((unsigned)C), dim3(DPREP_THREADS), dpl, st, nst, C,
+                             D, (const double*)a.mchol_rm, (const double*)a.minv, (double*)ns.zbuf,
+                             (double*)pv);
+        a.pv0 = pv;
+      }
+      a.zmom = ns.zbuf;
+      a.zrec = recs ? zr : nullptr;
+    }
+  }
+  if (GM_DENSE_PREP && a.dense_frozen && a.pv0 == nullptr) a.dense_frozen = 0;  // (no buffer)
+}
+
+// A window's end: the pooled metric from the window's rows (fewer than 5:
+// nothing changes), or maybe_update_mass_matrix for every chain. *refind: the
+// next launch starts with the probe + epsilon re-find.
+static int nuts_metric_update(NutsState& ns, gm_dtype dt, long long C, int D, bool pool_on, hipStream_t st,
+                              int* refind) {
+  if (pool_on) {
+    if (ns.p_rn < 5) return GM_OK;
+    const hipError_t e2 = dt == GM_F32 ? pooled_window_launch<float>(ns, C, D, 1, ns.p_rn * C, 1, 1, st)
+                                       : pooled_window_launch<double>(ns, C, D, 1, ns.p_rn * C, 1, 1, st);
+    if (e2 != hipSuccess) {
+      set_error(std::string("pooled window launch failed: ") + hipGetErrorString(e2));
+      return GM_EHIP;
+    }
+    ns.p_rn = 0;
+    *refind = 1;
+    return GM_OK;
+  }
+  const unsigned blocks = (unsigned)((C + 63) / 64);
+  if (dt == GM_F32)
+    hipLaunchKernelGGL(nuts_mass_update_kernel<float>, dim3(blocks), dim3(64), 0, st, C, D, ns.mass_mode,
+                       ns.convention, ns.m_reg, ns.m_jit, ns.mkind, (float*)ns.dinv, (float*)ns.dsq,
+                       (float*)ns.minv, (float*)ns.mchol, ns.rn, (float*)ns.rmean, (float*)ns.rm2d,
+                       (float*)ns.rm2, ns.updated, (float*)ns.mscratch);
+  else
+    hipLaunchKernelGGL(nuts_mass_update_kernel<double>, dim3(blocks), dim3(64), 0, st, C, D, ns.mass_mode,
+                       ns.convention, ns.m_reg, ns.m_jit, ns.mkind, (double*)ns.dinv, (double*)ns.dsq,
+                       (double*)ns.minv, (double*)ns.mchol, ns.rn, (double*)ns.rmean, (double*)ns.rm2d,
+                       (double*)ns.rm2, ns.updated, (double*)ns.mscratch);
+  const hipError_t e2 = hipGetLastError();
+  if (e2 != hipSuccess) {
+    set_error(std::string("mass update launch failed: ") + hipGetErrorString(e2));
+    return GM_EHIP;
+  }
+  *refind = 1;
+  return GM_OK;
+}
+
 int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay, void* q,
              long long* accepts, void* samples, long long C, int D, double target_accept,
              uint64_t seed, uint64_t* step, uint32_t chain_offset, long long total,
@@ -790,94 +990,33 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
   const uint64_t init_step = *step;
   const long long n_rows_total = step_mode ? 0 : progress ? total - n_discard : total - n_discard + 1;
   const long long row_shift = progress ? n_discard + 1 : n_discard;
-  // Launch segments: at most steps_per_launch transitions each, and a
-  // segment also ends at every warm-up window end, after which the metric
-  // update kernel runs and the next segment starts with the probe + epsilon
-  // re-find (generic_nuts.rs:897-921). The window schedule depends on m and
-  // n_discard only, so it is the same for every chain.
-  const long long chunk = steps_per_launch;
+  // Launch segments (gm_plan.h): at most steps_per_launch transitions each,
+  // and a segment also ends at every warm-up window end, after which the
+  // metric update kernel runs and the next segment starts with the probe +
+  // epsilon re-find (generic_nuts.rs:897-921). The window schedule depends on
+  // m and n_discard only, so it is the same for every chain.
   // The pooled metric: a warm-up launch stores its window rows (the positions
-  // the per-chain Welford state takes, sb < m < lim) to a scratch slab
-  // through the launch's sample arguments; after the launch the pooled
-  // statistics take the slab's rows on the stream (pivot at the window's
-  // first row, Gram partials, their fixed-order reduction: hmc_dense_kernels.hip),
-  // and a window end replaces every chain's metric.
+  // the per-chain Welford state takes, sb < m < lim) to a scratch slab through
+  // its sample arguments; pooled_accumulate then takes them on the stream, and
+  // a window end replaces every chain's metric.
   const bool pool_on = ns.pooled && ns.convention == 1 && ns.mass_mode && !step_mode && ns.pool != nullptr;
-  const long long plim = n_discard > ns.m_eb ? n_discard - ns.m_eb : 0;
-  const size_t row_bytes = (size_t)C * D * esz;
-  const long long slab_rows = std::max<long long>(1, (long long)((64u << 20) / row_bytes));
-  // gram row batches whose partials stay within 16 MiB
-  const long long gram_rb = std::max<long long>(1, (16LL << 20) / (long long)hmc_dense_gram_part_bytes(C, 1));
+  const long long slab_rows = pool_on ? slab_rows_for(C, D, esz) : 0;
+  // (a step runs past the warm-up, m > n_discard: no windows)
+  WindowSchedule sched = ns.sched;
+  const Plan plan = plan_nuts(sched, total, steps_per_launch, n_discard, ns.mass_mode && !step_mode, ns.m_sb, ns.m_eb,
+                              slab_rows);
+  const std::vector<Segment>& segs = plan.segs;
   if (pool_on) {
-    const long long wrows = std::min(plim - 1, total) - ns.m_sb;  // window rows of this run
-    if (wrows > 0) {  // both scratch buffers once, before anything is enqueued
-      const long long rows = std::min(std::min(slab_rows, chunk), wrows);
-      const size_t need = (size_t)rows * row_bytes;
-      const size_t pneed = hmc_dense_gram_part_bytes(C, (int)std::min(gram_rb, rows));
-      if (need > ns.slab_bytes) {
-        ffree(ns.slab);
-        ns.slab = nullptr;
-        ns.slab_bytes = 0;
-        if (hipMalloc(&ns.slab, need) == hipSuccess) ns.slab_bytes = need;
-      }
-      if (pneed > ns.ppart_bytes) {
-        ffree(ns.ppart);
-        ns.ppart = nullptr;
-        ns.ppart_bytes = 0;
-        if (hipMalloc(&ns.ppart, pneed) == hipSuccess) ns.ppart_bytes = pneed;
-      }
-      if (!ns.slab || !ns.ppart) {
-        (void)hipGetLastError();
-        set_error("pooled-metric scratch allocation failed");
-        return GM_ENOMEM;
-      }
+    const long long wrows = std::min(plan.lim - 1, total) - ns.m_sb;  // window rows of this run
+    // both scratch buffers once, before anything is enqueued
+    if (wrows > 0 && pooled_scratch_ensure(ns.ps, std::min(std::min(slab_rows, steps_per_launch), wrows), C, D, esz)) {
+      (void)hipGetLastError();
+      set_error("pooled-metric scratch allocation failed");
+      return GM_ENOMEM;
     }
   }
-  std::vector<long long> seg_start, seg_len;
-  std::vector<char> seg_update;
-  {
-    std::vector<long long> wends;
-    if (ns.mass_mode && !step_mode) {  // (a step runs past the warm-up: m > n_discard)
-      const long long lim = n_discard > ns.m_eb ? n_discard - ns.m_eb : 0;
-      for (long long m = 1; m <= total && m <= n_discard; ++m) {
-        if (m <= ns.m_sb || !(m < lim)) continue;  // should_collect
-        if (m >= ns.sched_next || m + 1 >= lim) {  // note_if_window_end
-          ns.sched_next += ns.sched_len;
-          ns.sched_len = ns.sched_len * 2 < 400 ? ns.sched_len * 2 : 400;
-          wends.push_back(m);
-        }
-      }
-    }
-    size_t wi = 0;
-    long long s0 = 0;
-    do {
-      long long n = total - s0 < chunk ? total - s0 : chunk;
-      if (n < 0) n = 0;
-      if (pool_on) {  // window rows (sb < m < lim) go to the slab: no more than it holds, nothing after them
-        const long long first = (s0 + 1 > ns.m_sb + 1) ? s0 + 1 : ns.m_sb + 1;
-        if (first < plim && first <= s0 + n) {
-          if (n > first - 1 - s0 + slab_rows) n = first - 1 - s0 + slab_rows;
-          if (n > plim - 1 - s0) n = plim - 1 - s0;
-        }
-      }
-      char upd = 0;
-      if (wi < wends.size() && wends[wi] <= s0 + n) {  // cut at the window end (step m = s0 + n)
-        n = wends[wi] - s0;
-        upd = 1;
-        ++wi;
-      }
-      seg_start.push_back(s0);
-      seg_len.push_back(n);
-      seg_update.push_back(upd);
-      s0 += n;
-    } while (s0 < total);
-    if (seg_update.back()) {  // an update on the last transition still re-finds epsilon
-      seg_start.push_back(total);
-      seg_len.push_back(0);
-      seg_update.push_back(0);
-    }
-  }
-  const long long n_launch = (long long)seg_start.size();
+  ns.sched = sched;
+  const long long n_launch = (long long)segs.size();
   while ((long long)evs.size() < 2 * n_launch) {
     hipEvent_t ev;
     if (hipEventCreate(&ev) != hipSuccess) {
@@ -897,43 +1036,14 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
       ns.p_rn = 0;
     }
   }
-  // The frozen-dense instantiation (MASS 3) for launches without a window
-  // end or Welford collection when every chain's metric is dense: read the
-  // chains' kinds back once (after the stream's earlier work)
   bool all_dense = false;
-  bool any_update = false;
-  for (char u : seg_update) any_update = any_update || u;
-  if (ns.mass_mode == 2 && !any_update && tg.kind != GM_TARGET_CUSTOM && lay.lanes == 16 && lay.elems == 2) {
-    std::vector<int> kinds((size_t)C);
-    if (hipMemcpyAsync(kinds.data(), ns.mkind, C * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-      set_error("copy of the NUTS metric kinds failed");
-      return GM_EHIP;
-    }
-    all_dense = C > 0;
-    for (int k : kinds) all_dense = all_dense && k == 2;
-  }
+  if (nuts_all_dense(ns, tg, lay, segs, C, st, &all_dense)) return GM_EHIP;
   int pending_refind = 0;
   uint64_t refind_step = 0;
-  NutsLdsBudget budget;
-  budget.lds_cap = ns.lds_levels_cap;  // gm_nuts_set_lds_levels (-1: as many as fit)
-  // dense M^-1 resident in LDS (layout 16 x 2) when it fits: full matrices
-  // or packed lower triangles (nuts_size_lds); gm_nuts_set_dense_forms picks
-  // packed only or global memory (identical results)
-  budget.minv_lds = ns.dense_minv_lds;
-  budget.chol_lds = ns.dense_chol_lds;
-  {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&budget.ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        budget.ncu < 1)
-      budget.ncu = 256;
-    if (hipDeviceGetAttribute(&budget.lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
-        budget.lds_max < 1)
-      budget.lds_max = 64 * 1024;
-  }
+  const NutsLdsBudget budget = nuts_lds_budget(ns);
   for (long long li = 0; li < n_launch; ++li) {
-    const long long start = seg_start[li], nst = seg_len[li];
+    const Segment& g = segs[li];
+    const long long start = g.start, nst = g.n;
     NutsRecLaunch a;  // (the kernels that do not record take its NutsLaunch part)
     a.q = q;
     a.accepts = accepts;
@@ -960,58 +1070,12 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
     a.t0 = start;
     a.row_shift = row_shift;
     a.n_rows = n_rows_total > 0 ? n_rows_total : 0;
-    long long used = 0;  // rows of this launch that enter the pooled statistics
-    if (pool_on) {  // transitions t = start + 1 .. start + nst with sb < t < lim
-      const long long first = std::max(start + 1, ns.m_sb + 1);
-      const long long hi = std::min(start + nst, plim - 1);
-      if (hi >= first) {  // (the segments were cut so that such a launch collects nothing and fits the slab)
-        used = hi - first + 1;
-        a.samples = ns.slab;
-        a.row_shift = first;
-        a.n_rows = used;
-      }
+    if (g.used > 0) {  // its window rows to the slab (cut so that such a launch collects nothing and fits it)
+      a.samples = ns.ps.slab;
+      a.row_shift = g.first_used;
+      a.n_rows = g.used;
     }
-    if (ns.mass_mode) {
-      a.mass_mode = ns.mass_mode;
-      a.mkind = ns.mkind;
-      a.dinv = ns.dinv;
-      a.dsq = ns.dsq;
-      a.minv = ns.minv;
-      a.mchol = ns.mchol;
-      a.mchol_rm = ns.mchol;
-      if (ns.mass_mode == 2) {  // the transposes, in the update kernel's scratch (free between its launches)
-        const size_t esz = dt == GM_F32 ? 4 : 8, cdd = (size_t)C * D * D * esz;
-        void* mT = ns.mscratch;
-        void* lT = (char*)ns.mscratch + cdd;
-        const long long n = C * (long long)D * D;
-        const unsigned tb = (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-        if (dt == GM_F32) {
-          hipLaunchKernelGGL(mat_transpose_kernel<float>, dim3(tb), dim3(256), 0, st, C, D, (const float*)ns.minv,
-                             (float*)mT);
-          hipLaunchKernelGGL(mat_transpose_kernel<float>, dim3(tb), dim3(256), 0, st, C, D,
-                             (const float*)ns.mchol, (float*)lT);
-        } else {
-          hipLaunchKernelGGL(mat_transpose_kernel<double>, dim3(tb), dim3(256), 0, st, C, D,
-                             (const double*)ns.minv, (double*)mT);
-          hipLaunchKernelGGL(mat_transpose_kernel<double>, dim3(tb), dim3(256), 0, st, C, D,
-                             (const double*)ns.mchol, (double*)lT);
-        }
-        a.minv = mT;
-        a.mchol = lT;
-      }
-      a.rn = ns.rn;
-      a.rmean = ns.rmean;
-      a.rm2d = ns.rm2d;
-      a.rm2 = ns.rm2;
-      a.updated = ns.updated;
-      a.sb = ns.m_sb;
-      a.eb = ns.m_eb;
-      a.do_refind = pending_refind;
-      a.refind_step = refind_step;
-      // no Welford collection in the launch: every m >= lim or m <= start_buffer
-      const long long lim = ns.n_discard > ns.m_eb ? ns.n_discard - ns.m_eb : 0;
-      a.dense_frozen = (all_dense && !a.do_refind && (a.m0 + 1 >= lim || a.m0 + nst <= ns.m_sb)) ? 1 : 0;
-    }
+    if (ns.mass_mode) nuts_mass_args(ns, dt, C, D, pending_refind, refind_step, all_dense, a, st);
     if (trk) {
       a.trk = *trk;
       a.trk.n0 = trk->n0 + (unsigned long long)start;
@@ -1022,80 +1086,7 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
       a.stats.t0 = stats->t0 + start;
     }
     hipEventRecord(evs[2 * li], st);
-    // the launch's momenta in one parallel pass ahead of the tree kernel
-    // (same values; skipped past GM_NUTS_ZBUF_MAX bytes, the kernel then draws
-    // them itself), timed with the launch
-    {
-      // [nst][C][D] momenta, then the start records [nst][C] (16-byte aligned)
-      const size_t nsc = (size_t)(nst > 0 ? nst : 0) * (size_t)C;
-      const size_t zmb = (nsc * (size_t)D * esz + 15) / 16 * 16;
-      const size_t zrb = nsc * (dt == GM_F32 ? sizeof(NutsStartRec<float>) : sizeof(NutsStartRec<double>));
-      // a frozen-dense launch (the MASS 3 kernel, 16 x 2): the metric applied
-      // in the pass as well, M^-1 p0 [nst][C][D] after the records
-      // (the frozen kernel is built for this pass, GM_DENSE_PREP: a launch the
-      // pass cannot serve -- pass off, buffer past its cap or not allocated --
-      // takes the adaptive dense kernel instead, the same bits)
-      const size_t dpl = (a.mass_mode == 2 && a.dense_frozen) ? nuts_dense_prep_lds(D, esz) : 0;
-      const size_t zvo = (zmb + zrb + 15) / 16 * 16;
-      if (GM_DENSE_PREP && a.dense_frozen &&
-          !(dpl > 0 && C <= 0x7fffffff && ns.momentum_pass && zvo + zmb <= (size_t)GM_NUTS_ZBUF_MAX))
-        a.dense_frozen = 0;
-      const bool dprep = GM_DENSE_PREP && a.dense_frozen;
-      const size_t zb = dprep ? zvo + zmb : zmb + zrb;
-      if (ns.momentum_pass && zb > 0 && zb <= (size_t)GM_NUTS_ZBUF_MAX) {
-        if (zb > ns.zbuf_bytes) {
-          if (ns.zbuf) hipFree(ns.zbuf);
-          ns.zbuf = nullptr;
-          ns.zbuf_bytes = 0;
-          // at most a quarter of the device memory free now: the buffer is
-          // kept for the sampler's later launches (gm_nuts_set_momentum_pass(s,
-          // 0) releases it), and must not crowd out other samplers' or the
-          // caller's allocations; without it the kernel draws its momenta
-          size_t fr = 0, tot = 0;
-          if (hipMemGetInfo(&fr, &tot) == hipSuccess && zb <= fr / 4 && hipMalloc(&ns.zbuf, zb) == hipSuccess)
-            ns.zbuf_bytes = zb;
-          else
-            (void)hipGetLastError();
-        }
-        if (ns.zbuf) {
-          const long long S = dt == GM_F32 ? 4 : 2;
-          const long long nb = (long long)((a.step0 + (uint64_t)nst - 1) / S - a.step0 / S + 1);
-          const long long work = nb * C * D;
-          const unsigned zbk = (unsigned)((work + 255) / 256 < 65536 ? (work + 255) / 256 : 65536);
-          void* zr = (char*)ns.zbuf + zmb;
-          const unsigned sbk = (unsigned)((nsc + 255) / 256 < 65536 ? (nsc + 255) / 256 : 65536);
-          // (the frozen-dense kernel draws its starts itself: GM_SREC_DENSE)
-          const bool recs = !(a.mass_mode == 2 && a.dense_frozen && !GM_SREC_DENSE);
-          if (dt == GM_F32) {
-            hipLaunchKernelGGL(nuts_momenta_kernel<float>, dim3(zbk), dim3(256), 0, st, seed, chain_offset, a.step0,
-                               nst, C, D, (float*)ns.zbuf);
-            if (recs)
-              hipLaunchKernelGGL(nuts_starts_kernel<float>, dim3(sbk), dim3(256), 0, st, seed, chain_offset, a.step0,
-                                 nst, C, ns.max_depth, (NutsStartRec<float>*)zr);
-          } else {
-            hipLaunchKernelGGL(nuts_momenta_kernel<double>, dim3(zbk), dim3(256), 0, st, seed, chain_offset,
-                               a.step0, nst, C, D, (double*)ns.zbuf);
-            if (recs)
-              hipLaunchKernelGGL(nuts_starts_kernel<double>, dim3(sbk), dim3(256), 0, st, seed, chain_offset,
-                                 a.step0, nst, C, ns.max_depth, (NutsStartRec<double>*)zr);
-          }
-          if (dprep) {  // p0 = L z in place of z, M^-1 p0 at zvo
-            void* pv = (char*)ns.zbuf + zvo;
-            if (dt == GM_F32)
-              hipLaunchKernelGGL(nuts_dense_momenta_kernel<float>, dim3((unsigned)C), dim3(DPREP_THREADS), dpl, st, nst, C, D,
-                                 (const float*)a.mchol_rm, (const float*)a.minv, (float*)ns.zbuf, (float*)pv);
-            else
-              hipLaunchKernelGGL(nuts_dense_momenta_kernel<double>, dim3((unsigned)C), dim3(DPREP_THREADS), dpl, st, nst, C,
-                                 D, (const double*)a.mchol_rm, (const double*)a.minv, (double*)ns.zbuf,
-                                 (double*)pv);
-            a.pv0 = pv;
-          }
-          a.zmom = ns.zbuf;
-          a.zrec = recs ? zr : nullptr;
-        }
-      }
-      if (GM_DENSE_PREP && a.dense_frozen && a.pv0 == nullptr) a.dense_frozen = 0;  // (no buffer)
-    }
+    nuts_momentum_pass(ns, dt, C, D, seed, chain_offset, a, st);
     hipError_t e;
     if (tg.kind == GM_TARGET_CUSTOM) {  // user target, runtime-compiled (gm_jit.cpp)
       const unsigned blocks = (unsigned)((C + 255) / 256);
@@ -1116,53 +1107,18 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
       set_error(std::string("NUTS launch failed: ") + hipGetErrorString(e));
       return GM_EHIP;
     }
-    if (used > 0) {  // the launch's window rows into s1 and S2, row after row (timed with the launch)
-      hipError_t e3 = hipSuccess;
-      if (ns.p_rn == 0) e3 = launch_hmc_dense_pivot(dt, ns.slab, C, D, ns.p_c0(D), st);
-      for (long long r = 0; r < used && e3 == hipSuccess; r += gram_rb) {
-        const int rows = (int)std::min(gram_rb, used - r);
-        e3 = launch_hmc_dense_gram(dt, (const char*)ns.slab + (size_t)r * row_bytes, rows, C, D, ns.p_c0(D),
-                                   (double*)ns.ppart, ns.p_s1(D), ns.p_S2(D), st);
-      }
+    if (g.used > 0) {  // the launch's window rows into s1 and S2, row after row (timed with the launch)
+      const hipError_t e3 = pooled_accumulate(dt, ns.ps, g.used, C, D, &ns.p_rn, ns.p_c0(D), ns.p_s1(D), ns.p_S2(D), st);
       if (e3 != hipSuccess) {
         set_error(std::string("pooled statistics launch failed: ") + hipGetErrorString(e3));
         return GM_EHIP;
       }
-      ns.p_rn += used;
     }
     hipEventRecord(evs[2 * li + 1], st);
     pending_refind = 0;
-    if (seg_update[li] && pool_on) {  // the pooled window end (fewer than 5 rows: nothing changes)
-      if (ns.p_rn >= 5) {
-        const hipError_t e2 = dt == GM_F32 ? pooled_window_launch<float>(ns, C, D, 1, ns.p_rn * C, 1, 1, st)
-                                           : pooled_window_launch<double>(ns, C, D, 1, ns.p_rn * C, 1, 1, st);
-        if (e2 != hipSuccess) {
-          set_error(std::string("pooled window launch failed: ") + hipGetErrorString(e2));
-          return GM_EHIP;
-        }
-        ns.p_rn = 0;
-        pending_refind = 1;
-        refind_step = *step + (uint64_t)(start + nst - 1);
-      }
-    } else if (seg_update[li]) {  // maybe_update_mass_matrix for every chain
-      const unsigned blocks = (unsigned)((C + 63) / 64);
-      if (dt == GM_F32)
-        hipLaunchKernelGGL(nuts_mass_update_kernel<float>, dim3(blocks), dim3(64), 0, st, C, D, ns.mass_mode,
-                           ns.convention, ns.m_reg, ns.m_jit, ns.mkind, (float*)ns.dinv, (float*)ns.dsq,
-                           (float*)ns.minv, (float*)ns.mchol, ns.rn, (float*)ns.rmean, (float*)ns.rm2d,
-                           (float*)ns.rm2, ns.updated, (float*)ns.mscratch);
-      else
-        hipLaunchKernelGGL(nuts_mass_update_kernel<double>, dim3(blocks), dim3(64), 0, st, C, D, ns.mass_mode,
-                           ns.convention, ns.m_reg, ns.m_jit, ns.mkind, (double*)ns.dinv, (double*)ns.dsq,
-                           (double*)ns.minv, (double*)ns.mchol, ns.rn, (double*)ns.rmean, (double*)ns.rm2d,
-                           (double*)ns.rm2, ns.updated, (double*)ns.mscratch);
-      hipError_t e2 = hipGetLastError();
-      if (e2 != hipSuccess) {
-        set_error(std::string("mass update launch failed: ") + hipGetErrorString(e2));
-        return GM_EHIP;
-      }
-      pending_refind = 1;
-      refind_step = *step + (uint64_t)(start + nst - 1);
+    if (g.update) {  // (a pooled window of fewer than 5 rows changes nothing)
+      if (nuts_metric_update(ns, dt, C, D, pool_on, st, &pending_refind)) return GM_EHIP;
+      if (pending_refind) refind_step = *step + (uint64_t)(start + nst - 1);
     }
     if (hook && *hook) {
       const int rc = (*hook)(start + nst);
