@@ -121,6 +121,8 @@ SIGNATURES = {
     "gm_sampler_set_steps_per_launch": (_ip, [_vp, _i64]),
     "gm_sampler_set_unroll": (_ip, [_vp, _i32]),
     "gm_sampler_last_unroll": (_ip, [_vp, C.POINTER(C.c_int32)]),
+    "gm_sampler_set_draw_waves": (_ip, [_vp, _i32]),
+    "gm_sampler_last_draw_waves": (_ip, [_vp, C.POINTER(C.c_int32)]),
     "gm_sampler_set_async": (_ip, [_vp, _i32]),
     "gm_sampler_synchronize": (_ip, [_vp]),
     "gm_sampler_reserve": (_ip, [_vp, _i64]),

@@ -293,6 +293,19 @@ class Sampler:
         _lib.check(self._lib.gm_sampler_last_unroll(self._h, C.byref(n)))
         return n.value
 
+    def set_draw_waves(self, n: int):
+        """HMC draw-wave form (the draws of a block made by waves of their own beside the chain
+        waves): -1 automatic, 0 off, or 1, 2 or 4 draw waves per workgroup where that count is
+        compiled (1, for the block leapfrog form), elsewhere as off; same results."""
+        _lib.check(self._lib.gm_sampler_set_draw_waves(self._h, int(n)))
+        return self
+
+    def last_draw_waves(self) -> int:
+        """The draw waves per workgroup of the last run's HMC launches (0: the form was off)."""
+        n = C.c_int32()
+        _lib.check(self._lib.gm_sampler_last_draw_waves(self._h, C.byref(n)))
+        return n.value
+
     def save_state(self) -> bytes:
         """Checkpoint (gm_state_save): positions, counters, seed and stream
         position, NUTS adaptation and metric. The reference has none

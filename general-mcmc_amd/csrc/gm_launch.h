@@ -74,6 +74,14 @@ constexpr int GM_LF_LONG = 7;
 // targets with `lf_block` (hmc_block_part.inc); every other kernel runs the
 // number as GM_LF_LONG, or as 1 where that is not compiled in either.
 constexpr int GM_LF_BLOCK = 49;
+// The draw-wave form of the block form (hmc_dw_device.h): the draw waves
+// beside the 4 chain waves of a workgroup, and the draw_waves /
+// gm_sampler_set_draw_waves number of the form. 1: one draw wave fills for
+// the four chains in turn (-3.5 % at the headline; 2: -2.7 %, 4: -0.6 %,
+// profiles/r12).
+#ifndef GM_DW_WAVES
+#define GM_DW_WAVES 1  // (measurement builds: 1, 2 or 4)
+#endif
 
 struct HmcLaunch {
   void* q = nullptr;            // [C*D] state, in/out
@@ -91,7 +99,8 @@ struct HmcLaunch {
   int collect_from = 0;         // steps s >= collect_from are stored ...
   long long sample_row0 = 0;    // ... at row sample_row0 + (s - collect_from)
   int lf_unroll = 1;            // leapfrog loop form (1, 2, 4, GM_LF_LONG or GM_LF_BLOCK; same results)
-  void* zs = nullptr;           // wide layouts: momentum block scratch [C][S][lanes*elems]
+  int draw_waves = 0;           // draw waves per workgroup (hmc_dw_device.h; 0: hmc_kernel; same results)
+  void* zs = nullptr;          // wide layouts: momentum block scratch [C][S][lanes*elems]
 };
 
 // ---- HMC with per-chain step sizes and a diagonal metric --------------------

@@ -115,6 +115,8 @@ struct gm_sampler {
   gm::Layout lay_wide{};            // ... and that layout
   long long steps_per_launch = 1000;
   int lf_unroll = 0;  // HMC leapfrog-loop form: 0 by the wave count and L (hmc_lf_unroll), else 1, 2, 4, GM_LF_LONG or GM_LF_BLOCK
+  int draw_waves = -1;  // HMC draw-wave form (hmc_dw_device.h): -1 by the regime (hmc_draw_waves), 0 off, else the draw waves per workgroup
+  int last_draw_waves = 0;  // the draw waves of the last run's launches (gm_sampler_last_draw_waves)
   std::vector<hipEvent_t> evs;
   double last_ms = 0;
   long long last_launches = 0;

@@ -801,6 +801,22 @@ int gm_sampler_last_unroll(gm_sampler* s, int32_t* n) {
   return GM_OK;
 }
 
+int gm_sampler_set_draw_waves(gm_sampler* s, int32_t n) {
+  GM_REQ(s, "sampler is NULL");
+  GM_REQ(n == -1 || n == 0 || n == 1 || n == 2 || n == 4,
+         "draw waves must be -1 (automatic), 0 (off), or 1, 2 or 4 per workgroup");
+  GM_REQ(!(n > 0 && s->st.mode), "sampler statistics (gm_sampler_set_stats) do not take the draw-wave form");
+  s->draw_waves = n;
+  return GM_OK;
+}
+
+int gm_sampler_last_draw_waves(gm_sampler* s, int32_t* n) {
+  GM_REQ(s, "sampler is NULL");
+  GM_REQ(n, "n is NULL");
+  *n = s->last_draw_waves;
+  return GM_OK;
+}
+
 int gm_sampler_reserve(gm_sampler* s, int64_t n_collect) {
   GM_REQ(s, "sampler is NULL");
   GM_REQ(n_collect >= 0, "n_collect must be >= 0");

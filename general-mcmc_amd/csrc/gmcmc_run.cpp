@@ -17,7 +17,7 @@ using namespace gm;
 // one wave per SIMD (latency bound), and 10-20% slower from two waves per
 // SIMD up.
 constexpr long long GM_LF_BLOCK_MIN_L1 = 2 * GM_LF_LONG;
-static int hmc_lf_unroll(long long waves, long long L, bool has_long, bool has_block) {
+static int device_simds() {
   static const int simds = [] {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -25,6 +25,10 @@ static int hmc_lf_unroll(long long waves, long long L, bool has_long, bool has_b
       cus = 256;
     return 4 * cus;
   }();
+  return simds;
+}
+static int hmc_lf_unroll(long long waves, long long L, bool has_long, bool has_block) {
+  const int simds = device_simds();
   // x4 at <= 1 wave per SIMD, x2 at <= 4 (the cfg2 headline), x1 above
   // (cfg4's 8 and the north star's 16 waves per SIMD), measured per regime
   const int form = waves <= simds ? 4 : waves <= 4 * simds ? 2 : 1;
@@ -39,6 +43,20 @@ static int hmc_lf_unroll(long long waves, long long L, bool has_long, bool has_b
     return GM_LF_LONG;
   }
   return form;
+}
+
+// The draw-wave form of the block form (hmc_dw_device.h, identical results):
+// GM_DW_WAVES draw waves per workgroup where the launch runs the block form in
+// the regime in which the form measured faster (profiles/r12): f32, above
+// two and a half and up to four chain waves per SIMD (3000 and 4096 chains:
+// -3.5 %; 2048 and 1029: +2 %), and a leapfrog loop of at most one pass
+// (L = 15 to 50: -3.5 to -5 %; L = 99: +4.7 %). Elsewhere off.
+static int hmc_draw_waves(long long waves, long long L, int lf_unroll, bool has_block, bool f32) {
+  const int simds = device_simds();
+  return has_block && f32 && lf_unroll == GM_LF_BLOCK && L - 1 <= GM_LF_BLOCK && 2 * waves > 5 * simds &&
+                 waves <= 4 * simds
+             ? GM_DW_WAVES
+             : 0;
 }
 
 // hipSetDevice only when the calling thread is on another device (the call
@@ -249,9 +267,21 @@ int run_steps(gm_sampler* s, long long total, long long collect_from, int progre
   const bool has_long = !adapt_path && s->lay.lanes == 64 && s->lay.elems == 1;
   // (the block form: hmc_part.inc, the targets with lf_block)
   const bool has_block = has_long && s->tg.kind == GM_TARGET_ROSENBROCK;
+  const long long waves = (s->C * s->lay.lanes + 63) / 64;
+  // (a forced draw-wave count takes the block form with it where the loop
+  // form is left to the rule: the draw-wave form is compiled for that one)
+  const bool dw_forced = s->kind == K_HMC && has_block && s->draw_waves == GM_DW_WAVES;
   const int lf_unroll = s->kind != K_HMC ? 1 : s->lf_unroll ? s->lf_unroll
-                                                             : hmc_lf_unroll((s->C * s->lay.lanes + 63) / 64, s->L, has_long, has_block);
+                        : dw_forced      ? GM_LF_BLOCK
+                                         : hmc_lf_unroll(waves, s->L, has_long, has_block);
   s->last_unroll = lf_unroll;
+  // the draw waves of this run's launches: the rule, or the forced count where
+  // the form is compiled (the block form's kernels at GM_DW_WAVES), else off
+  const int draw_waves = s->kind != K_HMC || !has_block || lf_unroll != GM_LF_BLOCK ? 0
+                         : s->draw_waves < 0 ? hmc_draw_waves(waves, s->L, lf_unroll, has_block, s->dt == GM_F32)
+                         : s->draw_waves == GM_DW_WAVES ? GM_DW_WAVES
+                                                        : 0;
+  s->last_draw_waves = draw_waves;
   const HmcPath path = s->kind != K_HMC ? P_MH : !adapt_path ? P_PLAIN : s->hd.on ? P_DENSE : P_ADAPT;
   // The first `warm` transitions are the warm-up, cut at every metric window's
   // end (diagonal: mode 2) and at its own end.
@@ -281,6 +311,7 @@ int run_steps(gm_sampler* s, long long total, long long collect_from, int progre
       a.eps = s->eps;
       a.L = s->L;
       a.lf_unroll = lf_unroll;
+      a.draw_waves = draw_waves;
       if (path == P_PLAIN) {
         if (layout_is_wide(s->lay)) a.zs = s->d_zs;  // the momentum scratch
         e = launch_hmc(s->dt, s->tg, s->lay, a, s->stream, ev);

@@ -3,7 +3,8 @@
 // translation unit per dtype so that they build in parallel), hmc_wide_kernel
 // by hmc_kernels.hip, and hmc_kernel at run time for user targets by
 // gm_jit.cpp. The algorithm notes are at the top of hmc_kernels.hip, which
-// also holds launch_hmc, the one entry point of all three.
+// also holds launch_hmc, the one entry point of all three. The draw-wave
+// form of hmc_kernel's block form is hmc_dw_kernel (hmc_dw_device.h).
 #pragma once
 #include "gm_device.h"
 #include "gm_launch.h"
@@ -187,7 +188,13 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
     }
     const T ke0 = kesA[K];
     // prefetch the next block (if this launch reaches it)
+#ifdef GM_MEASURE_REUSE_DRAWS
+    // (measurement builds only, never shipped: no draw block after the
+    // launch's first, block A reused; wrong numbers, the time without fill)
+    if (false) {
+#else
     if (K == phase && more) {
+#endif
       fill(zsB, kesB, lusB, lwN, opens_window(blk + 1), blk + 1);
       hasB = true;
     }
@@ -357,7 +364,11 @@ __global__ __launch_bounds__(256) void hmc_kernel(HmcLaunch a, TG tg_) {
         if constexpr (W1) {
           if (opens_window(blk)) lw = lwN;
         }
+#ifdef GM_MEASURE_REUSE_DRAWS
+      } else if (s == 0) {
+#else
       } else {
+#endif
         // the launch's first block, or the one after a first block that began
         // past this wave's prefetch position (its window is already in lw
         // unless it opens a new one)

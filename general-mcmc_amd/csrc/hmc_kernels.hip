@@ -16,6 +16,12 @@
 // The gradient at the current point is carried across transitions (the
 // reference re-evaluates it twice per step, batched_hmc.rs:138,169; same
 // values), so a transition costs exactly L target evaluations.
+//
+// The draws of a transition (momenta, their kinetic energy, ln u) depend on
+// (seed, chain id, transition index) alone. hmc_kernel makes them a draw block
+// ahead inside the chain's own wave; the draw-wave form of its block form
+// (hmc_dw_device.h, chosen per launch: HmcLaunch::draw_waves) gives them to a
+// wave of their own beside the four chain waves of a workgroup.
 #include "hmc_device.h"
 #include "gm_jit.h"
 #include "gm_layouts.h"

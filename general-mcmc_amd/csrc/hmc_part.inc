@@ -7,6 +7,8 @@
 namespace gm {
 // hmc_kernel<T, 64, 1, RosenbrockT<T>, GM_LF_BLOCK> (hmc_block_f32.hip, hmc_block_f64.hip)
 hipError_t launch_hmc_block(const RosenbrockT<GM_HMC_T>& t, const HmcLaunch& a, hipStream_t st, LaunchEvents ev);
+// hmc_dw_kernel<T, RosenbrockT<T>, GM_DW_WAVES> (hmc_dw_f32.hip, hmc_dw_f64.hip)
+hipError_t launch_hmc_dw(const RosenbrockT<GM_HMC_T>& t, const HmcLaunch& a, hipStream_t st, LaunchEvents ev);
 
 hipError_t GM_HMC_NAME(const TargetDev& tg, const Layout& lay, const HmcLaunch& a, hipStream_t st,
                        LaunchEvents ev) {
@@ -26,6 +28,8 @@ hipError_t GM_HMC_NAME(const TargetDev& tg, const Layout& lay, const HmcLaunch& 
       // lf_block, in a unit of its own (hmc_block_part.inc); elsewhere the
       // number runs the long form
       if constexpr (E == 1 && requires { TG::lf_block; }) {
+        // ... and its draw-wave form (hmc_dw_part.inc) where the launch asks for it
+        if (a.lf_unroll == GM_LF_BLOCK && a.draw_waves == GM_DW_WAVES) return launch_hmc_dw(t, a, st, ev);
         if (a.lf_unroll == GM_LF_BLOCK) return launch_hmc_block(t, a, st, ev);
       }
       if (a.lf_unroll == GM_LF_LONG || a.lf_unroll == GM_LF_BLOCK)

@@ -508,6 +508,22 @@ int gm_sampler_set_unroll(gm_sampler* s, int32_t n);
 /* The form the last run's HMC launches took (the automatic choice resolved). */
 int gm_sampler_last_unroll(gm_sampler* s, int32_t* n);
 
+/* HMC draw-wave form of the fused kernel: the momenta, their kinetic energies
+ * and the accept log-uniforms of a draw block are made by waves of their own
+ * beside the chain waves of a workgroup and handed over through LDS, one
+ * barrier per draw block. -1 (default) chosen by the regime in which it
+ * measured faster, 0 off, or n = 1, 2 or 4 draw waves per 4 chain waves
+ * forced. The form is compiled for the block leapfrog form (unroll 49: one
+ * chain per wave, one element per lane, RosenbrockND; a forced n takes that
+ * loop form with it where the unroll is automatic) at n = 1; a launch that
+ * is not of that kind, or another n, runs as off. Refused (n > 0) while
+ * sampler statistics are on. Tests and measurements; identical results
+ * either way. No reference counterpart. */
+int gm_sampler_set_draw_waves(gm_sampler* s, int32_t n);
+/* The draw waves per workgroup of the last run's HMC launches (0: the form
+ * was off). */
+int gm_sampler_last_draw_waves(gm_sampler* s, int32_t* n);
+
 /* Pre-size the device sample buffer for runs collecting up to n_collect
  * transitions, so that a later gm_run / gm_run_device does no device
  * allocation (the buffer only grows; hmc.rs:164-181 allocates its output on

@@ -18,6 +18,7 @@ p.add_argument("--steps", type=int, default=100)
 p.add_argument("--rounds", type=int, default=5)
 p.add_argument("--dtype", default="f32")
 p.add_argument("--layouts", default="64x1,32x2,16x4,8x8" )
+p.add_argument("--draw-waves", type=int, default=None, help="set_draw_waves(n) on every sampler (libraries that have it)")
 a = p.parse_args()
 dt = np.float32 if a.dtype == "f32" else np.float64
 x0 = gm.init_with_seed(a.chains, a.dim, 42, dt)
@@ -30,6 +31,8 @@ for lay in lays:
     except gm.GMError as e:
         print("skip", lay, e)
         continue
+    if a.draw_waves is not None and hasattr(s._lib, "gm_sampler_set_draw_waves"):
+        s.set_draw_waves(a.draw_waves)
     s.run_positions(0, 20)
     samplers[lay] = s
 res = {lay: [] for lay in samplers}
