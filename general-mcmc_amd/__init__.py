@@ -11,7 +11,7 @@ from .core import init, init_det, init_with_seed
 from .distributions import (CustomTarget, DenseGaussian, DiffableGaussian2D, Gaussian2D,
                             IsotropicGaussian, Rosenbrock2D, RosenbrockND)
 from .hmc import HMC, HMCAdaptConfig
-from .metropolis_hastings import MetropolisHastings
+from .metropolis_hastings import MetropolisHastings, MHAdaptConfig
 from .nuts import NUTS, MassMatrix, NUTSChain, NUTSMassMatrixConfig
 from .stats import (BasicStats, ChainStats, MultiChainTracker, Progress, RunStats, SamplerStats, StatsSummary, Summary,
                     basic_stats, rank_normalize, split_rhat_mean_ess, summary)
@@ -22,5 +22,5 @@ __all__ = [
     "init_det",
     "init_with_seed", "split_rhat_mean_ess", "basic_stats", "BasicStats", "RunStats", "GMError",
     "batch_vector", "MultiChainTracker", "ChainStats", "Progress", "NUTSMassMatrixConfig", "MassMatrix",
-    "HMCAdaptConfig", "Summary", "summary", "rank_normalize", "SamplerStats", "StatsSummary",
+    "HMCAdaptConfig", "MHAdaptConfig", "Summary", "summary", "rank_normalize", "SamplerStats", "StatsSummary",
 ]

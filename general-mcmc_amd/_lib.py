@@ -84,6 +84,11 @@ SIGNATURES = {
     "gm_hmc_set_dense_metric": (_ip, [_vp, _vp]),
     "gm_hmc_get_dense_metric": (_ip, [_vp, _vp, _vp, _vp, _vp]),
     "gm_mh_create": (_ip, [C.POINTER(gm_target), _ip, _i64, _i64, _vp, _dbl, _i64, C.POINTER(_vp)]),
+    "gm_mh_set_adaptation": (_ip, [_vp, _i32, _dbl, _i64, _i64, _i64, _dbl, _dbl]),
+    "gm_mh_set_proposal_scales": (_ip, [_vp, _vp]),
+    "gm_mh_get_proposal_scales": (_ip, [_vp, _vp, _vp]),
+    "gm_mh_set_proposal_diag": (_ip, [_vp, _vp]),
+    "gm_mh_get_proposal_diag": (_ip, [_vp, _vp]),
     "gm_nuts_create": (_ip, [C.POINTER(gm_target), _ip, _i64, _i64, _vp, _dbl, _i32, _i64, C.POINTER(_vp)]),
     "gm_set_seed": (_ip, [_vp, _u64]),
     "gm_step": (_ip, [_vp]),

@@ -134,6 +134,14 @@ hipError_t launch_stats_reduce(gm_dtype dt, const void* rec, long long C, long l
 // ---- MH --------------------------------------------------------------------
 hipError_t launch_mh(gm_dtype dt, const TargetDev& tg, const Layout& lay, const MhLaunch& a,
                      hipStream_t st, LaunchEvents ev = {});
+// per-chain proposal scale / diagonal shape / warm-up (mh_adapt_kernels.hip);
+// mode: 0 frozen, 1 scale adaptation, 2 scale + Welford statistics
+hipError_t launch_mh_adapt(gm_dtype dt, const TargetDev& tg, const Layout& lay, const MhAdaptLaunch& a, int mode,
+                           hipStream_t st, LaunchEvents ev = {});
+// a warm-up window's end (rn >= 5): shape from the Welford state, restart of the dual averaging
+hipError_t launch_mh_adapt_window(gm_dtype dt, long long C, int D, double regularize, double jitter, long long rn,
+                                  void* scale, const void* scale_bar, void* h_bar, void* mu, void* diag,
+                                  void* rmean, void* rm2, hipStream_t st);
 
 // ---- target evaluation -----------------------------------------------------
 // one leapfrog of n chains, state in HBM (util_device.h leapfrog_hbm_kernel)

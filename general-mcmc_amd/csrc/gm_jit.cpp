@@ -17,14 +17,17 @@ namespace {
 
 const char* kKernelHeader[] = {"hmc_device.h", "mh_device.h", "nuts_device.h", "util_device.h",
                                "hmc_adapt_device.h", "hmc_adapt_device.h", "hmc_adapt_device.h",
-                               "hmc_dense_device.h", "hmc_dense_device.h", "nuts_device.h"};
+                               "hmc_dense_device.h", "hmc_dense_device.h", "nuts_device.h",
+                               "mh_adapt_device.h", "mh_adapt_device.h", "mh_adapt_device.h"};
 const char* kKernelName[] = {"hmc_kernel", "mh_kernel", "nuts_kernel", "logp_grad_kernel",
                              "hmc_adapt_kernel", "hmc_adapt_kernel", "hmc_adapt_kernel",
-                             "hmc_dense_kernel", "hmc_dense_kernel", "nuts_kernel"};
+                             "hmc_dense_kernel", "hmc_dense_kernel", "nuts_kernel",
+                             "mh_adapt_kernel", "mh_adapt_kernel", "mh_adapt_kernel"};
 // the kernel's trailing template argument, if any: the NUTS metric handling
 // (user targets run with or without mass-matrix adaptation from one module),
-// the MODE of hmc_adapt_kernel and of hmc_dense_kernel
-const char* kKernelTail[] = {"", "", ", 2", "", ", 0", ", 1", ", 2", ", 0", ", 1", ", 2, true"};
+// the MODE of hmc_adapt_kernel, of hmc_dense_kernel and of mh_adapt_kernel
+const char* kKernelTail[] = {"", "", ", 2", "", ", 0", ", 1", ", 2", ", 0", ", 1", ", 2, true",
+                             ", 0", ", 1", ", 2"};
 
 // The adapter between the user's function and the engine's target concept
 // (bind / lds_bytes / eval, gm_device.h): one chain per lane, so E = dim and

@@ -6,7 +6,7 @@
 //     template <class T> __device__ T gm_logp_grad(const T* x, T* g, const T* params);
 // for one chain's position x[GM_DIM] (GM_DIM is a macro), writing the gradient
 // to g and returning the log-density. gm_jit.cpp compiles the engine's own
-// sampler kernels (hmc_device.h, hmc_adapt_device.h, hmc_dense_device.h, mh_device.h, nuts_device.h, util_device.h)
+// sampler kernels (hmc_device.h, hmc_adapt_device.h, hmc_dense_device.h, mh_device.h, mh_adapt_device.h, nuts_device.h, util_device.h)
 // around it for the one-chain-per-lane layout (lanes 1, elems = dim), with
 // the same flags as the ahead-of-time build, and caches the code per process.
 #pragma once
@@ -34,7 +34,11 @@ enum JitKernel {
   JIT_HMC_DENSE0 = 7,
   JIT_HMC_DENSE1 = 8,
   // nuts_kernel with the per-transition records (REC)
-  JIT_NUTS_REC = 9
+  JIT_NUTS_REC = 9,
+  // mh_adapt_kernel (mh_adapt_device.h), MODE 0, 1, 2
+  JIT_MH_ADAPT0 = 10,
+  JIT_MH_ADAPT1 = 11,
+  JIT_MH_ADAPT2 = 12
 };
 
 // Host mirror of the device adapter gm::UserTarget<T> (kernel argument).

@@ -178,6 +178,26 @@ struct MhLaunch {
   TrackLaunch trk;              // run_progress chain trackers (off when trk.mean is null)
 };
 
+// ---- MH with a per-chain proposal scale and a per-chain diagonal shape -------
+// (mh_adapt_device.h). A launch is wholly frozen (MODE 0) or wholly warm-up
+// (MODE 1 scale, MODE 2 scale + Welford statistics): the host cuts launches at
+// the warm-up's end and at every window end, as for HmcAdaptLaunch.
+struct MhAdaptLaunch {
+  MhLaunch m;                   // as for the plain kernel (m.prop_std unused)
+  void* scale = nullptr;        // [C] per-chain proposal scale, in/out while adapting
+  void* scale_bar = nullptr;    // [C] in/out (MODE >= 1)
+  void* h_bar = nullptr;        // [C] in/out (MODE >= 1)
+  const void* mu = nullptr;     // [C]
+  const void* diag = nullptr;   // [C][D] proposal shape, or null: all ones
+  void* rmean = nullptr;        // [C][D] Welford mean, in/out (MODE 2)
+  void* rm2 = nullptr;          // [C][D] Welford sum of squared deviations, in/out (MODE 2)
+  double delta = 0.234;         // target acceptance
+  long long k0 = 0;             // dual-averaging restart counter before this launch
+  long long rn0 = 0;            // Welford count before this launch
+  long long m0 = 0;             // warm-up transitions before this launch (m = m0 + s + 1)
+  long long sb = 0, lim = 0;    // Welford collects while sb < m < lim (lim = n_discard - end_buffer)
+};
+
 // ---- NUTS ------------------------------------------------------------------
 // bytes of one HBM subtree-stack entry: three D-vectors, alpha, n, n_alpha,
 // padded to whole 128-byte cache lines

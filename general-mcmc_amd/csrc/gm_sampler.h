@@ -46,6 +46,23 @@ struct HmcAdapt {
   void *dinv = nullptr, *dsq = nullptr, *rmean = nullptr, *rm2 = nullptr;         // [C][D]
 };
 
+// MH with a per-chain proposal scale, a per-chain diagonal proposal shape and
+// their warm-up (gm_mh_set_*; mh_adapt_device.h). `has`: the per-chain arrays
+// [C] exist and the sampler runs mh_adapt_kernel instead of mh_kernel. The
+// [C][D] arrays exist only once a shape was set or mode 2 was armed (`has_diag`);
+// without them the shape is all ones.
+struct MhAdapt {
+  bool has = false, has_diag = false;
+  int mode = 0;        // 0 none, 1 scale, 2 scale + diagonal shape
+  bool armed = false;  // the next run's n_discard transitions are the warm-up
+  double delta = 0.234;
+  long long sb = 0, eb = 0, iw = 0;
+  double reg = 0, jit = 0;
+  long long k = 0, rn = 0;  // dual-averaging restart counter and Welford count (the same for every chain)
+  void *scale = nullptr, *scale_bar = nullptr, *h_bar = nullptr, *mu = nullptr;  // [C]
+  void *diag = nullptr, *rmean = nullptr, *rm2 = nullptr;                        // [C][D]
+};
+
 // One dense metric shared by all chains (gm_hmc_set_dense_*;
 // hmc_dense_device.h). `on`: the sampler runs hmc_dense_kernel. The per-chain
 // step sizes, the dual-averaging state, the window configuration and the
@@ -129,6 +146,7 @@ struct gm_sampler {
   gm::NutsState nuts;
   HmcAdapt ha;
   HmcDense hd;
+  MhAdapt ma;
   StatsRun st;
   // run_progress statistics: per-chain trackers (MH, NUTS) and a
   // MultiChainTracker (HMC), one allocation each (TrackSet)

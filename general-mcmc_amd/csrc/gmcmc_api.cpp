@@ -488,11 +488,14 @@ int gm_custom_target_check(const char* source, gm_dtype dtype, int64_t dim, int3
   GM_REQ(source, "source is NULL");
   GM_REQ(dtype == GM_F32 || dtype == GM_F64, "bad dtype");
   GM_REQ(dim >= 1 && dim <= GM_CUSTOM_MAX_DIM, "CUSTOM targets support dim in [1, 256]");
-  GM_REQ(kind >= 0 && kind <= 5, "kind: 0 logp/grad, 1 HMC, 2 MH, 3 NUTS, 4 HMC warm-up, 5 HMC dense metric");
+  GM_REQ(kind >= 0 && kind <= 6,
+         "kind: 0 logp/grad, 1 HMC, 2 MH, 3 NUTS, 4 HMC warm-up, 5 HMC dense metric, 6 MH warm-up");
   GM_REQ(kind != 5 || (dim >= 2 && dim <= GM_DENSE_MAX_DIM), "the dense metric takes 2 <= dim <= 64");
-  // 4, 5: hmc_adapt_kernel (MODE 2) and hmc_dense_kernel (MODE 1) in their most general instantiations
+  // 4, 5, 6: hmc_adapt_kernel (MODE 2), hmc_dense_kernel (MODE 1) and mh_adapt_kernel (MODE 2) in their most
+  // general instantiations
   const JitKernel jk = kind == 1 ? JIT_HMC : kind == 2 ? JIT_MH : kind == 3 ? JIT_NUTS
-                       : kind == 4 ? JIT_HMC_ADAPT2 : kind == 5 ? JIT_HMC_DENSE1 : JIT_LOGP;
+                       : kind == 4 ? JIT_HMC_ADAPT2 : kind == 5 ? JIT_HMC_DENSE1
+                       : kind == 6 ? JIT_MH_ADAPT2 : JIT_LOGP;
   return jit_compile(jk, dtype, source, (int)dim);
 }
 
@@ -1062,6 +1065,7 @@ int gm_run_progress_cb(gm_sampler* s, int64_t n_collect, int64_t n_discard, void
       t_last = clk::now();
       return GM_OK;
     };
+    if (s->kind == K_MH) s->ha.pending_warm = n_discard;  // (an armed MH warm-up, gm_mh_set_adaptation)
     rc = run_steps(s, total, n_discard, 1, &tl, cb ? &hook : nullptr, chunk);
     if (rc) return rc;
     s->trk_n = (unsigned long long)total;
@@ -1559,6 +1563,254 @@ int gm_hmc_get_dense_metric(gm_sampler* s, double* minv, double* a_factor, int64
   return GM_OK;
 }
 
+// ---- MH warm-up: per-chain proposal scale and diagonal shape (MhAdapt) -------
+static void mh_adapt_free(MhAdapt& h) {
+  for (void** p : {&h.scale, &h.scale_bar, &h.h_bar, &h.mu, &h.diag, &h.rmean, &h.rm2}) {
+    if (*p) hipFree(*p);
+    *p = nullptr;
+  }
+  h = MhAdapt();
+}
+
+// A proposal scale at which mh_kernel takes its `cancel` form (mh_device.h:
+// the same arithmetic in the sampler dtype), the only form mh_adapt_kernel has:
+// finite and > 0, 2 scale^2 a normal number, the proposal's constant finite.
+extern "C++" {
+template <class T> static bool mh_scale_ok_t(double v, int D) {
+  const T sd = (T)v;
+  if (!(sd > (T)0) || !std::isfinite(sd)) return false;
+  const T var = sd * sd;
+  const T two_var = (T)2 * var;
+  const T pi = (T)3.14159265358979323846;
+  const T qconst = (-(T)D * (T)0.5) * glog(((var * pi) * sd) * sd);
+  return std::isnormal(two_var) && std::isfinite(qconst);
+}
+}  // extern "C++"
+static bool mh_scale_ok(const gm_sampler* s, double v) {
+  return s->dt == GM_F32 ? mh_scale_ok_t<float>(v, s->D) : mh_scale_ok_t<double>(v, s->D);
+}
+static double mh_std_rounded(const gm_sampler* s) {
+  return s->dt == GM_F32 ? (double)(float)s->prop_std : s->prop_std;
+}
+
+// The gm_mh_set_* / gm_mh_get_* calls need an MH sampler (GM_ESTATE).
+static int mh_adapt_callable(gm_sampler* s) {
+  GM_REQ(s, "sampler is NULL");
+  if (s->kind != K_MH) {
+    set_error("per-chain proposal scales, the diagonal proposal shape and their warm-up are for MH samplers");
+    return GM_ESTATE;
+  }
+  return GM_OK;
+}
+
+// Allocates the per-chain arrays [C] in their start state: every scale the
+// creation proposal_std, no statistics. From here on the sampler runs
+// mh_adapt_kernel. The caller has checked the scales the sampler will run with.
+static int mh_adapt_ensure(gm_sampler* s) {
+  MhAdapt& h = s->ma;
+  if (h.has) return GM_OK;
+  if (s->tg.kind == GM_TARGET_CUSTOM) {  // a source that does not compile for this kernel fails here
+    const int rc = jit_prepare(JIT_MH_ADAPT0, s->dt, s->tg);
+    if (rc) return rc;
+  }
+  const size_t C = (size_t)s->C;
+  hipError_t e = hipSuccess;
+  for (void** p : {&h.scale, &h.scale_bar, &h.h_bar, &h.mu})
+    if (e == hipSuccess) e = hipMalloc(p, C * s->esz);
+  if (e == hipSuccess) e = hipMemset(h.h_bar, 0, C * s->esz);
+  if (e == hipSuccess) e = hipMemset(h.mu, 0, C * s->esz);
+  if (e != hipSuccess) {
+    mh_adapt_free(h);
+    set_error(std::string("per-chain MH state allocation failed: ") + hipGetErrorString(e));
+    return GM_ENOMEM;
+  }
+  std::vector<double> v(C, s->prop_std);
+  int rc = put_as(s->dt, v.data(), C, h.scale);
+  if (!rc) rc = put_as(s->dt, v.data(), C, h.scale_bar);
+  if (rc) {
+    const std::string msg = gm_last_error();
+    mh_adapt_free(h);
+    set_error(msg);
+    return rc;
+  }
+  h.has = true;
+  return GM_OK;
+}
+
+// ... and the [C][D] arrays: the all-ones shape, no statistics.
+static int mh_adapt_ensure_diag(gm_sampler* s) {
+  MhAdapt& h = s->ma;
+  if (h.has_diag) return GM_OK;
+  const size_t CD = (size_t)s->C * (size_t)s->D;
+  hipError_t e = hipSuccess;
+  for (void** p : {&h.diag, &h.rmean, &h.rm2})
+    if (e == hipSuccess) e = hipMalloc(p, CD * s->esz);
+  if (e == hipSuccess) e = hipMemset(h.rmean, 0, CD * s->esz);
+  if (e == hipSuccess) e = hipMemset(h.rm2, 0, CD * s->esz);
+  int rc = GM_OK;
+  if (e != hipSuccess) {
+    set_error(std::string("per-chain MH shape allocation failed: ") + hipGetErrorString(e));
+    rc = GM_ENOMEM;
+  } else {
+    std::vector<double> v(CD, 1.0);
+    rc = put_as(s->dt, v.data(), CD, h.diag);
+  }
+  if (rc) {
+    const std::string msg = gm_last_error();
+    for (void** p : {&h.diag, &h.rmean, &h.rm2}) {
+      if (*p) hipFree(*p);
+      *p = nullptr;
+    }
+    set_error(msg);
+    return rc;
+  }
+  h.has_diag = true;
+  return GM_OK;
+}
+static void mh_adapt_drop_diag(MhAdapt& h) {
+  for (void** p : {&h.diag, &h.rmean, &h.rm2}) {
+    if (*p) hipFree(*p);
+    *p = nullptr;
+  }
+  h.has_diag = false;
+}
+
+int gm_mh_set_adaptation(gm_sampler* s, int32_t mode, double target_accept, int64_t start_buffer,
+                         int64_t end_buffer, int64_t initial_window, double regularize, double jitter) {
+  int rc = mh_adapt_callable(s);
+  if (rc) return rc;
+  GM_REQ(mode >= 0 && mode <= 2, "mode must be 0 (off), 1 (scale) or 2 (scale + diagonal shape)");
+  GM_REQ(target_accept > 0 && target_accept < 1, "target_accept must be in (0, 1)");
+  GM_REQ(start_buffer >= 0 && end_buffer >= 0 && initial_window >= 0, "window sizes must be >= 0");
+  GM_REQ(regularize >= 0 && regularize <= 1, "regularize must be in [0, 1]");
+  GM_REQ(!std::isnan(jitter), "jitter is NaN");
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  if (mode == 0) {  // back to the creation proposal_std and mh_kernel
+    mh_adapt_free(s->ma);
+    return GM_OK;
+  }
+  const size_t C = (size_t)s->C;
+  std::vector<double> e(C, mh_std_rounded(s)), mu(C);
+  if (s->ma.has) {
+    rc = get_as(s->dt, s->ma.scale, C, e.data());
+    if (rc) return rc;
+  }
+  for (size_t c = 0; c < C; ++c) {
+    GM_REQ(mh_scale_ok(s, e[c]),
+           "proposal scales must be finite and > 0, with 2 scale^2 a normal number of the dtype, to be adapted");
+    mu[c] = std::log(10.0 * e[c]);
+  }
+  if (s->tg.kind == GM_TARGET_CUSTOM) {
+    rc = jit_prepare(mode == 1 ? JIT_MH_ADAPT1 : JIT_MH_ADAPT2, s->dt, s->tg);
+    if (rc) return rc;
+  }
+  rc = mh_adapt_ensure(s);
+  if (!rc && mode == 2) rc = mh_adapt_ensure_diag(s);
+  if (rc) return rc;
+  MhAdapt& h = s->ma;
+  // start state: scale_bar = scale, mu = ln(10 scale), h_bar = 0, k = 0, no statistics
+  GM_HIP(hipMemcpy(h.scale_bar, h.scale, C * s->esz, hipMemcpyDeviceToDevice));
+  rc = put_as(s->dt, mu.data(), C, h.mu);
+  if (rc) return rc;
+  GM_HIP(hipMemset(h.h_bar, 0, C * s->esz));
+  if (h.has_diag) {
+    GM_HIP(hipMemset(h.rmean, 0, C * s->D * s->esz));
+    GM_HIP(hipMemset(h.rm2, 0, C * s->D * s->esz));
+  }
+  h.mode = mode;
+  h.armed = true;
+  h.delta = target_accept;
+  h.sb = start_buffer;
+  h.eb = end_buffer;
+  h.iw = initial_window;
+  h.reg = regularize;
+  h.jit = jitter;
+  h.k = 0;
+  h.rn = 0;
+  return GM_OK;
+}
+
+int gm_mh_set_proposal_scales(gm_sampler* s, const double* scale) {
+  int rc = mh_adapt_callable(s);
+  if (rc) return rc;
+  GM_REQ(scale, "scale is NULL");
+  const size_t C = (size_t)s->C;
+  for (size_t c = 0; c < C; ++c)
+    GM_REQ(mh_scale_ok(s, scale[c]),
+           "proposal scales must be finite and > 0, with 2 scale^2 a normal number of the dtype");
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  rc = mh_adapt_ensure(s);
+  if (rc) return rc;
+  rc = put_as(s->dt, scale, C, s->ma.scale);
+  if (!rc) rc = put_as(s->dt, scale, C, s->ma.scale_bar);
+  if (rc) return rc;
+  if (s->ma.armed) {  // an armed warm-up starts from these: mu = ln(10 scale)
+    std::vector<double> mu(C);
+    for (size_t c = 0; c < C; ++c) mu[c] = std::log(10.0 * (s->dt == GM_F32 ? (double)(float)scale[c] : scale[c]));
+    rc = put_as(s->dt, mu.data(), C, s->ma.mu);
+  }
+  return rc;
+}
+
+int gm_mh_get_proposal_scales(gm_sampler* s, double* scale, double* scale_bar) {
+  int rc = mh_adapt_callable(s);
+  if (rc) return rc;
+  const size_t C = (size_t)s->C;
+  if (!s->ma.has) {
+    for (size_t c = 0; c < C; ++c) {
+      if (scale) scale[c] = mh_std_rounded(s);
+      if (scale_bar) scale_bar[c] = mh_std_rounded(s);
+    }
+    return GM_OK;
+  }
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  if (scale) rc = get_as(s->dt, s->ma.scale, C, scale);
+  if (!rc && scale_bar) rc = get_as(s->dt, s->ma.scale_bar, C, scale_bar);
+  return rc;
+}
+
+int gm_mh_set_proposal_diag(gm_sampler* s, const void* diag) {
+  int rc = mh_adapt_callable(s);
+  if (rc) return rc;
+  GM_REQ(diag, "diag is NULL");
+  const size_t n = (size_t)s->C * s->D;
+  for (size_t i = 0; i < n; ++i) {  // checked in full before anything changes
+    const double v = s->dt == GM_F32 ? (double)((const float*)diag)[i] : ((const double*)diag)[i];
+    GM_REQ(v > 0 && std::isfinite(v), "diag entries must be finite and > 0");
+  }
+  // (a sampler without per-chain scales goes on with the creation proposal_std in every chain)
+  GM_REQ(s->ma.has || mh_scale_ok(s, s->prop_std),
+         "the creation proposal_std is outside the per-chain path: 2 std^2 must be a normal number of the dtype");
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  rc = mh_adapt_ensure(s);
+  if (!rc) rc = mh_adapt_ensure_diag(s);
+  if (rc) return rc;
+  GM_HIP(hipMemcpy(s->ma.diag, diag, n * s->esz, hipMemcpyHostToDevice));
+  return GM_OK;
+}
+
+int gm_mh_get_proposal_diag(gm_sampler* s, void* diag) {
+  int rc = mh_adapt_callable(s);
+  if (rc) return rc;
+  GM_REQ(diag, "diag is NULL");
+  const size_t n = (size_t)s->C * s->D;
+  if (!s->ma.has_diag) {
+    for (size_t i = 0; i < n; ++i) {
+      if (s->dt == GM_F32) ((float*)diag)[i] = 1.0f;
+      else ((double*)diag)[i] = 1.0;
+    }
+    return GM_OK;
+  }
+  GM_HIP(hipSetDevice(s->device));
+  GM_HIP(hipStreamSynchronize(s->stream));
+  GM_HIP(hipMemcpy(diag, s->ma.diag, n * s->esz, hipMemcpyDeviceToHost));
+  return GM_OK;
+}
+
 int gm_nuts_get_step_size(gm_sampler* s, double* eps, double* eps_bar) {
   GM_REQ(s, "sampler is NULL");
   GM_REQ(s->kind == K_NUTS, "not a NUTS sampler");
@@ -1734,7 +1986,9 @@ struct StateHeader {
   // NUTS warm-up fields: m_sb, m_eb, sched_len = initial_window, m_reg,
   // m_jit, target_accept, nuts_m = mode | armed << 8, nuts_n_discard = k,
   // sched_next = rn. A sampler without that state writes 0 here and zeros
-  // there, as it always did.
+  // there, as it always did. MH: 1 when the blob carries per-chain proposal
+  // scales (MhAdapt), 2 when the [C][D] shape and Welford arrays follow them;
+  // configuration and counters in the same fields as HMC's.
   int32_t mass_mode;
   int64_t m_sb, m_eb, sched_next, sched_len;
   double m_reg, m_jit;
@@ -1785,6 +2039,12 @@ std::vector<StatePart> state_parts_for(gm_sampler* s, int mass_mode) {
     for (void* p : {h.eps, h.eps_bar, h.h_bar, h.mu}) v.push_back({p, C * e});
     for (void* p : {h.dinv, h.dsq, h.rmean, h.rm2}) v.push_back({p, C * D * e});
   }
+  if (s->kind == K_MH && mass_mode) {
+    MhAdapt& h = s->ma;
+    for (void* p : {h.scale, h.scale_bar, h.h_bar, h.mu}) v.push_back({p, C * e});
+    if (mass_mode == 2)
+      for (void* p : {h.diag, h.rmean, h.rm2}) v.push_back({p, C * D * e});
+  }
   if (s->kind == K_HMC && mass_mode == 2) {  // the dense metric: float64 masters, counters, pooled statistics
     HmcDense& d = s->hd;
     v.push_back({d.minv, D * D * 8});
@@ -1805,6 +2065,7 @@ int state_mode(gm_sampler* s) {
   if (s->kind == K_NUTS)
     return s->nuts.mass_mode |
            ((s->nuts.convention ? 1 : 0) | (s->nuts.pooled ? 2 : 0) | (s->nuts.pool ? 4 : 0)) << 8;
+  if (s->kind == K_MH) return s->ma.has ? (s->ma.has_diag ? 2 : 1) : 0;
   return s->kind == K_HMC && s->ha.has ? (s->hd.on ? 2 : 1) : 0;
 }
 size_t state_bytes(gm_sampler* s) { return parts_bytes(state_parts_for(s, state_mode(s))); }
@@ -1903,6 +2164,19 @@ int gm_state_save(gm_sampler* s, void* out, uint64_t bytes) {
     h.nuts_n_discard = a.k;
     h.sched_next = a.rn;
   }
+  if (s->kind == K_MH && s->ma.has) {
+    const MhAdapt& a = s->ma;
+    h.mass_mode = a.has_diag ? 2 : 1;
+    h.m_sb = a.sb;
+    h.m_eb = a.eb;
+    h.sched_len = a.iw;
+    h.m_reg = a.reg;
+    h.m_jit = a.jit;
+    h.target_accept = a.delta;
+    h.nuts_m = a.mode | (a.armed ? 1 << 8 : 0);
+    h.nuts_n_discard = a.k;
+    h.sched_next = a.rn;
+  }
   unsigned char* o = (unsigned char*)out;
   memcpy(o, &h, sizeof(h));
   o += sizeof(h);
@@ -1943,6 +2217,12 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
       break;
     case K_MH:
       GM_REQ(h.prop_std == s->prop_std, "state blob is for a different proposal std");
+      GM_REQ(h.mass_mode >= 0 && h.mass_mode <= 2, "corrupt state blob (per-chain state flag)");
+      if (h.mass_mode)
+        GM_REQ((h.nuts_m & 0xff) <= 2 && (h.nuts_m & ~0x1ffLL) == 0 && h.nuts_n_discard >= 0 &&
+                   h.sched_next >= 0 && h.m_sb >= 0 && h.m_eb >= 0 && h.sched_len >= 0 &&
+                   ((h.nuts_m & 0xff) != 2 || !((h.nuts_m >> 8) & 1) || h.mass_mode == 2),
+               "corrupt state blob (warm-up configuration)");
       break;
     case K_NUTS:
       GM_REQ(h.target_accept == s->target_accept && h.max_depth == s->max_depth,
@@ -1958,7 +2238,6 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
       GM_REQ(h.nuts_m >= 0 && h.nuts_n_discard >= 0 && h.sched_len >= 0, "corrupt state blob (counters)");
       break;
   }
-  if (s->kind == K_MH) GM_REQ(h.mass_mode == 0, "corrupt state blob (mass mode)");
   GM_REQ(bytes >= parts_bytes(state_parts_for(s, h.mass_mode)), "state blob too short");
   GM_HIP(hipSetDevice(s->device));
   GM_HIP(hipStreamSynchronize(s->stream));
@@ -1981,6 +2260,16 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
     } else {
       hmc_dense_free(s);
       hmc_adapt_free(s);  // the blob's sampler ran the plain path
+    }
+  }
+  if (s->kind == K_MH) {
+    if (h.mass_mode) {
+      int rc = mh_adapt_ensure(s);
+      if (!rc && h.mass_mode == 2) rc = mh_adapt_ensure_diag(s);
+      if (rc) return rc;
+      if (h.mass_mode != 2) mh_adapt_drop_diag(s->ma);
+    } else {
+      mh_adapt_free(s->ma);  // the blob's sampler ran the plain path
     }
   }
   const unsigned char* p = (const unsigned char*)in + sizeof(h);
@@ -2019,6 +2308,19 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
       const int rc = hmc_dense_put_copies(s, mi.data(), af.data());
       if (rc) return rc;
     }
+  }
+  if (s->kind == K_MH && h.mass_mode) {
+    MhAdapt& a = s->ma;
+    a.sb = h.m_sb;
+    a.eb = h.m_eb;
+    a.iw = h.sched_len;
+    a.reg = h.m_reg;
+    a.jit = h.m_jit;
+    a.delta = h.target_accept;
+    a.mode = (int)(h.nuts_m & 0xff);
+    a.armed = (h.nuts_m >> 8) & 1;
+    a.k = h.nuts_n_discard;
+    a.rn = h.sched_next;
   }
   return GM_OK;
 }
@@ -2110,6 +2412,7 @@ int gm_destroy(gm_sampler* s) {
   nuts_free_state(&s->nuts);
   hmc_adapt_free(s);
   hmc_dense_free(s);
+  mh_adapt_free(s->ma);
   hmc_adapt_free(s->st.ident);
   if (s->st.buf) hipFree(s->st.buf);
   if (s->st.scratch) hipFree(s->st.scratch);

@@ -120,7 +120,9 @@ static StatsLaunch stats_launch(const gm_sampler* s, long long pos) {
 // recording run of a plain one: hmc_adapt_kernel's frozen mode with the
 // identity state of StatsRun, the same bits) takes P_ADAPT, one with the dense
 // metric P_DENSE.
-enum HmcPath { P_MH, P_PLAIN, P_ADAPT, P_DENSE };
+// An MH sampler with per-chain proposal scales (gm_mh_set_*) takes
+// P_MH_ADAPT, mh_adapt_kernel.
+enum HmcPath { P_MH, P_MH_ADAPT, P_PLAIN, P_ADAPT, P_DENSE };
 
 // the launch fields the MH kernel and every HMC kernel take (MhLaunch,
 // HmcLaunch), for segment g storing rows c
@@ -151,6 +153,55 @@ static hipError_t launch_mh_seg(const gm_sampler* s, const Segment& g, Collect c
     a.trk.n0 = trk->n0 + (unsigned long long)g.start;
   }
   return launch_mh(s->dt, s->tg, s->lay, a, s->stream, ev);
+}
+
+// Per-chain proposal scales / diagonal shape: a warm-up launch (MODE 1 or 2)
+// is followed by mh_adapt_window_kernel at a window's end and by
+// scale = scale_bar at the warm-up's end; the rest is frozen (MODE 0). Nothing
+// here waits for the device, so asynchronous runs stay asynchronous.
+static hipError_t launch_mh_adapt_seg(gm_sampler* s, const Segment& g, Collect c, const TrackLaunch* trk,
+                                      long long warm, long long lim, LaunchEvents ev) {
+  MhAdapt& h = s->ma;
+  const bool in_warm = g.start < warm;
+  MhAdaptLaunch a;
+  a.m = launch_args<MhLaunch>(s, g, c);
+  a.m.prop_std = s->prop_std;
+  if (trk) {
+    a.m.trk = *trk;
+    a.m.trk.n0 = trk->n0 + (unsigned long long)g.start;
+  }
+  a.scale = h.scale;
+  a.scale_bar = h.scale_bar;
+  a.h_bar = h.h_bar;
+  a.mu = h.mu;
+  a.diag = h.diag;
+  a.rmean = h.rmean;
+  a.rm2 = h.rm2;
+  a.delta = h.delta;
+  a.k0 = h.k;
+  a.rn0 = h.rn;
+  a.m0 = g.start;
+  a.sb = h.sb;
+  a.lim = lim;
+  // (the window-end update and the copy below go before the run's stop event)
+  LaunchEvents kev = ev;
+  if (in_warm) kev.stop = nullptr;
+  hipError_t e = launch_mh_adapt(s->dt, s->tg, s->lay, a, in_warm ? h.mode : 0, s->stream, kev);
+  if (e != hipSuccess || !in_warm) return e;
+  h.k += g.n;
+  h.rn += g.used;  // (mode 2: its transitions m with sb < m < lim)
+  if (g.update && h.rn >= 5) {  // (fewer than 5 positions: nothing changes, the statistics are kept)
+    e = launch_mh_adapt_window(s->dt, s->C, s->D, h.reg, h.jit, h.rn, h.scale, h.scale_bar, h.h_bar, h.mu, h.diag,
+                               h.rmean, h.rm2, s->stream);
+    h.k = 0;
+    h.rn = 0;
+  }
+  if (e == hipSuccess && g.start + g.n == warm) {  // the warm-up is over: scale = scale_bar, frozen from here on
+    h.armed = false;
+    e = hipMemcpyAsync(h.scale, h.scale_bar, (size_t)s->C * s->esz, hipMemcpyDeviceToDevice, s->stream);
+  }
+  if (e == hipSuccess && ev.stop) e = hipEventRecord(ev.stop, s->stream);
+  return e;
 }
 
 // the warm-up is over: eps = eps_bar, frozen from here on
@@ -282,14 +333,22 @@ int run_steps(gm_sampler* s, long long total, long long collect_from, int progre
                          : s->draw_waves == GM_DW_WAVES ? GM_DW_WAVES
                                                         : 0;
   s->last_draw_waves = draw_waves;
-  const HmcPath path = s->kind != K_HMC ? P_MH : !adapt_path ? P_PLAIN : s->hd.on ? P_DENSE : P_ADAPT;
+  const HmcPath path = s->kind != K_HMC ? (s->ma.has ? P_MH_ADAPT : P_MH)
+                       : !adapt_path     ? P_PLAIN
+                       : s->hd.on        ? P_DENSE
+                                         : P_ADAPT;
   // The first `warm` transitions are the warm-up, cut at every metric window's
   // end (diagonal: mode 2) and at its own end.
   HmcAdapt& h = s->ha.has ? s->ha : s->st.ident;
-  const long long warm = path >= P_ADAPT && s->ha.armed && s->ha.mode ? std::min(pending_warm, total) : 0;
+  const MhAdapt& mh = s->ma;
+  const long long warm = path >= P_ADAPT && s->ha.armed && s->ha.mode ? std::min(pending_warm, total)
+                         : path == P_MH_ADAPT && mh.armed && mh.mode  ? std::min(pending_warm, total)
+                                                                      : 0;
   const long long slab_rows = path == P_DENSE ? slab_rows_for(s->C, s->D, s->esz) : 0;
-  const Plan plan = plan_hmc(total, chunk, warm, path == P_DENSE || (path == P_ADAPT && h.mode == 2), h.sb, h.eb,
-                             h.iw, slab_rows);
+  const Plan plan = path == P_MH_ADAPT
+                        ? plan_hmc(total, chunk, warm, mh.mode == 2, mh.sb, mh.eb, mh.iw, 0)
+                        : plan_hmc(total, chunk, warm, path == P_DENSE || (path == P_ADAPT && h.mode == 2), h.sb, h.eb,
+                                   h.iw, slab_rows);
   // scratch once, before anything is enqueued
   if (path == P_DENSE && warm > 0 && plan.lim - 1 > h.sb)
     rc = pooled_scratch_ensure(s->hd.ps, std::min(std::min(slab_rows, chunk), plan.lim - 1 - h.sb), s->C, s->D,
@@ -306,6 +365,8 @@ int run_steps(gm_sampler* s, long long total, long long collect_from, int progre
     hipError_t e;
     if (path == P_MH) {
       e = launch_mh_seg(s, g, c, trk, ev);
+    } else if (path == P_MH_ADAPT) {
+      e = launch_mh_adapt_seg(s, g, c, trk, warm, plan.lim, ev);
     } else {
       HmcLaunch a = launch_args<HmcLaunch>(s, g, c);
       a.eps = s->eps;

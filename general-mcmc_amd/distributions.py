@@ -206,12 +206,13 @@ class CustomTarget(_TargetBase):
         t.n_params = self.params.size
         return [src, self.params]
 
-    _KINDS = {"logp": 0, "hmc": 1, "mh": 2, "nuts": 3, "hmc_adapt": 4, "hmc_dense": 5}
+    _KINDS = {"logp": 0, "hmc": 1, "mh": 2, "nuts": 3, "hmc_adapt": 4, "hmc_dense": 5, "mh_adapt": 6}
 
     def check(self, sampler: str = "hmc", dtype=np.float64) -> None:
         """Compile the source into `sampler`'s kernel ("hmc", "mh", "nuts",
         "hmc_adapt": HMC with per-chain step sizes / metric / warm-up,
-        "hmc_dense": HMC with the dense metric, 2 <= dim <= 64, or "logp")
+        "hmc_dense": HMC with the dense metric, 2 <= dim <= 64, "mh_adapt": MH
+        with per-chain proposal scales / shape / warm-up, or "logp")
         without running it; raises GMError with the compiler log."""
         lib = _lib.load()
         _lib.check(lib.gm_custom_target_check(self.source.encode(), _lib.dtype_code(dtype), self.dim,

@@ -86,7 +86,8 @@ typedef struct gm_target {
 
 /* Compile a CUSTOM target's source for the sampler kernels without running it
  * (kind: 1 HMC, 2 MH, 3 NUTS, 4 HMC with per-chain step sizes / metric /
- * warm-up, 5 HMC with a dense metric (2 <= dim <= 64),
+ * warm-up, 5 HMC with a dense metric (2 <= dim <= 64), 6 MH with per-chain
+ * proposal scales / shape / warm-up,
  * 0 log-density/gradient); GM_EINVAL with the
  * compiler log in gm_last_error() when it does not compile. */
 int gm_custom_target_check(const char* source, gm_dtype dtype, int64_t dim, int32_t kind);
@@ -227,6 +228,57 @@ int gm_hmc_get_dense_metric(gm_sampler* s, double* minv, double* a_factor, int64
 int gm_mh_create(const gm_target* target, gm_dtype dtype, int64_t n_chains, int64_t dim,
                  const void* init, double proposal_std, int64_t chain_offset,
                  gm_sampler** out);
+
+/* ---- MH warm-up: a per-chain proposal scale and a per-chain diagonal shape ----
+ * No reference counterpart (the reference's MH takes one IsotropicGaussian).
+ * A sampler on which none of these calls was made runs exactly as before.
+ * They need an MH sampler (GM_ESTATE otherwise).
+ *
+ * With per-chain state a transition of chain c proposes
+ *   y[i] = x[i] + z[i] * f[i],   f[i] = scale[c] * diag[c][i]
+ * from the plain path's proposal normals z (f rounded to the sampler dtype
+ * once per chain, coordinate and scale value; product and sum are two
+ * roundings) and accepts iff lp(y) - lp(x) > ln u: the proposal is symmetric.
+ * diag is a standard deviation per coordinate, all ones unless set or adapted;
+ * with diag == 1 and scale[c] == s the transition has the bits of the plain
+ * path at proposal_std = s. The per-chain path exists where the plain kernel
+ * drops the proposal's cancelling log-density terms: every scale finite and
+ * > 0 with 2 scale^2 a normal number of the sampler dtype and a finite
+ * proposal constant (GM_EINVAL otherwise, the sampler unchanged; the creation
+ * proposal_std is held to the same when these calls start from it).
+ *
+ * gm_mh_set_adaptation arms a warm-up exactly as gm_hmc_set_adaptation does:
+ * the n_discard transitions of the next gm_run* call adapt (n_discard == 0
+ * adapts nothing and stays armed; gm_step never starts one; calling it again
+ * re-arms from the current scales). Mode 1 adapts the scale per chain after
+ * every warm-up transition by the dual averaging of the HMC warm-up (gamma
+ * .05, t0 10, kappa .75, mu = ln(10 scale) at the start and at each restart)
+ * on alpha = min(1, exp(log_alpha)), NaN -> 0; after the last warm-up
+ * transition scale = scale_bar. Mode 2 adds Welford statistics of the
+ * post-accept position while start_buffer < m < n_discard - end_buffer in the
+ * windows of the shared schedule (initial_window doubling up to 400); at a
+ * window end with >= 5 positions diag = sqrt(max((1 - regularize) var +
+ * regularize, max(jitter, 1e-10))), the statistics reset and the dual
+ * averaging restarts from scale_bar. Mode 0 drops all per-chain state: the
+ * sampler is back on the creation proposal_std, the plain kernel and the
+ * plain checkpoint. Recommended: target_accept 0.234, buffers 75 / 150,
+ * initial_window 25, regularize 0.05, jitter 1e-6.
+ * GM_EINVAL unless 0 < target_accept < 1, the window sizes are >= 0,
+ * regularize is in [0, 1] and mode is 0, 1 or 2. */
+int gm_mh_set_adaptation(gm_sampler* s, int32_t mode /* 0 off, 1 scale, 2 scale + diagonal shape */,
+                         double target_accept, int64_t start_buffer, int64_t end_buffer,
+                         int64_t initial_window, double regularize, double jitter);
+/* Per-chain proposal scales scale[n_chains] (rounded to the sampler dtype);
+ * scale_bar is set to the same values. */
+int gm_mh_set_proposal_scales(gm_sampler* s, const double* scale);
+/* Per-chain (scale, scale_bar), [n_chains] each, either may be NULL; the
+ * creation proposal_std for every chain before any of these calls. */
+int gm_mh_get_proposal_scales(gm_sampler* s, double* scale, double* scale_bar);
+/* The proposal shape diag [n_chains][dim] of the sampler dtype, every entry
+ * finite and > 0 (GM_EINVAL otherwise, the sampler unchanged). */
+int gm_mh_set_proposal_diag(gm_sampler* s, const void* diag);
+/* diag [n_chains][dim] of the sampler dtype; ones before any of these calls. */
+int gm_mh_get_proposal_diag(gm_sampler* s, void* diag);
 
 /* NUTS::new (nuts.rs:156-180) -> GenericNUTS::new (generic_nuts.rs:370-377):
  * identity mass matrix, dual-averaging step size (gamma .05, t0 10, kappa .75).
