@@ -8,7 +8,7 @@ every transition computed by hand-written gfx950 HIP kernels in libgmcmc.so
 from . import _lib, batch_vector
 from ._lib import GMError
 from .core import init, init_det, init_with_seed
-from .distributions import (CustomTarget, DenseGaussian, DiffableGaussian2D, Gaussian2D,
+from .distributions import (GLM, CustomTarget, DenseGaussian, DiffableGaussian2D, Gaussian2D,
                             IsotropicGaussian, Rosenbrock2D, RosenbrockND)
 from .hmc import HMC, HMCAdaptConfig
 from .metropolis_hastings import MetropolisHastings, MHAdaptConfig
@@ -18,7 +18,7 @@ from .stats import (BasicStats, ChainStats, MultiChainTracker, Progress, RunStat
 
 __all__ = [
     "HMC", "NUTS", "NUTSChain", "MetropolisHastings", "RosenbrockND", "Rosenbrock2D",
-    "IsotropicGaussian", "DiffableGaussian2D", "DenseGaussian", "Gaussian2D", "CustomTarget", "init",
+    "IsotropicGaussian", "DiffableGaussian2D", "DenseGaussian", "Gaussian2D", "CustomTarget", "GLM", "init",
     "init_det",
     "init_with_seed", "split_rhat_mean_ess", "basic_stats", "BasicStats", "RunStats", "GMError",
     "batch_vector", "MultiChainTracker", "ChainStats", "Progress", "NUTSMassMatrixConfig", "MassMatrix",

@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("GMCMC_LIB", os.path.join(_HERE, "lib", "libgmcmc.so")
 GM_OK, GM_EINVAL, GM_EHIP, GM_ENOMEM, GM_ERCCL, GM_ESTATE = range(6)
 GM_F32, GM_F64 = 0, 1
 GM_TARGET_ROSENBROCK, GM_TARGET_ISO_GAUSS, GM_TARGET_GAUSS, GM_TARGET_CUSTOM = 1, 2, 3, 4
+GM_TARGET_GLM = 5
+GM_GLM_BERNOULLI_LOGIT, GM_GLM_POISSON_LOG = 1, 2
 UNIQUE_ID_BYTES = 128
 
 
@@ -25,6 +27,18 @@ class GMError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"[gmcmc status {code}] {msg}")
         self.code = code
+
+
+class gm_glm_desc(C.Structure):
+    _fields_ = [
+        ("family", C.c_int32),
+        ("reserved", C.c_int32),
+        ("n_rows", C.c_int64),
+        ("x", C.POINTER(C.c_double)),
+        ("y", C.POINTER(C.c_double)),
+        ("offset", C.POINTER(C.c_double)),
+        ("prior_sd", C.POINTER(C.c_double)),
+    ]
 
 
 class gm_target(C.Structure):
@@ -41,6 +55,7 @@ class gm_target(C.Structure):
         ("source", C.c_char_p),
         ("params", C.POINTER(C.c_double)),
         ("n_params", C.c_int64),
+        ("glm", C.POINTER(gm_glm_desc)),  # appended; read only when kind == GM_TARGET_GLM
     ]
 
 

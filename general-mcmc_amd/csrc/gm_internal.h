@@ -22,6 +22,11 @@ struct TargetDev {
   const void* prec = nullptr;  // [D*D] of the sampler dtype, transposed (prec[j*D+i] = P_ij)
   const char* src = nullptr;     // CUSTOM: user source (interned, lives for the process)
   const void* params = nullptr;  // CUSTOM: [n_params] of the sampler dtype
+  // GLM (glm_device.h): one device allocation of the sampler dtype,
+  // iv [Dp] | y [Np] | offset [Np] | xt [Dp][Np]
+  const void* glm = nullptr;
+  int glm_family = 0, glm_dp = 0;
+  long long glm_n = 0, glm_np = 0;
 };
 
 struct Layout {
@@ -35,6 +40,10 @@ bool wide_layout_supported(int lanes, int elems, gm_dtype dt);
 // largest dim of the wide path (f32; f64 is half of it)
 constexpr int GM_WIDE_MAX_DIM = 16384;
 Layout default_layout(int D, gm_dtype dt, int kind);
+// the GLM target's own layouts and kernel entry points (glm_kernels.hip,
+// glm_hmc_adapt_*.hip, glm_nuts_*.hip)
+bool glm_layout_supported(int lanes, int elems);
+Layout glm_default_layout(int D);
 Layout nuts_wide_default(int D, gm_dtype dt);
 bool nuts_wide_layout_supported(int lanes, int elems);  // nuts_wide.hip
 
@@ -73,6 +82,11 @@ hipError_t launch_hmc(gm_dtype dt, const TargetDev& tg, const Layout& lay, const
 // mode: 0 frozen, 1 step-size adaptation, 2 step size + Welford statistics
 hipError_t launch_hmc_adapt(gm_dtype dt, const TargetDev& tg, const Layout& lay, const HmcAdaptLaunch& a,
                             int mode, hipStream_t st, LaunchEvents ev = {});
+// the same kernels for the GLM target at its own layouts
+hipError_t launch_glm_hmc_adapt(gm_dtype dt, const TargetDev& tg, const Layout& lay, const HmcAdaptLaunch& a, int mode,
+                                hipStream_t st, LaunchEvents ev);
+hipError_t launch_glm_logp_grad(gm_dtype dt, const TargetDev& tg, const Layout& lay, long long n, const void* x,
+                                void* logp, void* grad, hipStream_t st);
 // a warm-up window's end (rn >= 5): metric from the Welford state, restart of the dual averaging
 hipError_t launch_hmc_adapt_window(gm_dtype dt, long long C, int D, double regularize, double jitter,
                                    long long rn, void* eps, const void* eps_bar, void* h_bar, void* mu,

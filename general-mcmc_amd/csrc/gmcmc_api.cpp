@@ -77,6 +77,7 @@ Layout default_layout(int D, gm_dtype dt, int kind) {
     l.elems = D;
     return l;
   }
+  if (kind == GM_TARGET_GLM) return glm_default_layout(D);  // its own layout list (glm_layouts.h)
   if (D > 1024) {
     // wide: the smallest elems whose workgroup holds the chain, so that a
     // chain gets as many waves as possible (few huge chains fill more of the
@@ -322,6 +323,7 @@ static int hmc_dense_callable(gm_sampler* s) {
     set_error("the dense metric and its warm-up are for HMC samplers");
     return GM_ESTATE;
   }
+  GM_REQ(s->tg.kind != GM_TARGET_GLM, "GLM target: the dense HMC metric is not supported");
   GM_REQ(s->D >= 2 && s->D <= GM_DENSE_MAX_DIM, "the dense metric takes 2 <= dim <= 64");
   const Layout def = default_layout(s->D, s->dt, s->tg.kind);
   GM_REQ(s->lay.lanes == def.lanes && s->lay.elems == def.elems,
@@ -399,6 +401,63 @@ static int hmc_dense_ensure(gm_sampler* s) {
   return GM_OK;
 }
 
+// GLM target: validation (the first offending row or column by name), then
+// one device allocation iv [Dp] | y [Np] | offset [Np] | xt [Dp][Np] of the
+// sampler dtype (glm_layouts.h glm_target): rows padded to a multiple of 256,
+// columns to a multiple of 32, X transposed, the padding zero.
+static int build_glm(const gm_target* t, gm_dtype dt, long long dim, TargetDev* out, void** d_buf) {
+  const gm_glm_desc* g = t->glm;
+  GM_REQ(g != nullptr, "GLM target: the description (gm_target.glm) is NULL");
+  GM_REQ(g->family == GM_GLM_BERNOULLI_LOGIT || g->family == GM_GLM_POISSON_LOG,
+         "GLM target: family must be GM_GLM_BERNOULLI_LOGIT (1) or GM_GLM_POISSON_LOG (2)");
+  GM_REQ(dim >= 1 && dim <= 128, "GLM target: dim must be in [1, 128]");
+  GM_REQ(g->n_rows >= 1, "GLM target: n_rows must be >= 1");
+  GM_REQ(g->n_rows <= (1LL << 24), "GLM target: n_rows must be <= 2^24");
+  GM_REQ(g->x != nullptr && g->y != nullptr && g->prior_sd != nullptr, "GLM target: x, y and prior_sd must not be NULL");
+  const long long N = g->n_rows, D = dim;
+  auto fail = [](const std::string& m) {
+    set_error(m);
+    return GM_EINVAL;
+  };
+  for (long long j = 0; j < D; ++j) {
+    if (!std::isfinite(g->prior_sd[j])) return fail("GLM target: prior_sd is not finite at column " + std::to_string(j));
+    if (!(g->prior_sd[j] > 0)) return fail("GLM target: prior_sd must be > 0 at column " + std::to_string(j));
+  }
+  for (long long n = 0; n < N; ++n) {
+    for (long long j = 0; j < D; ++j)
+      if (!std::isfinite(g->x[n * D + j]))
+        return fail("GLM target: x is not finite at row " + std::to_string(n) + ", column " + std::to_string(j));
+    const double yn = g->y[n];
+    if (!std::isfinite(yn)) return fail("GLM target: y is not finite at row " + std::to_string(n));
+    if (g->family == GM_GLM_BERNOULLI_LOGIT && !(yn >= 0 && yn <= 1))
+      return fail("GLM target: bernoulli_logit needs 0 <= y <= 1 at row " + std::to_string(n));
+    if (g->family == GM_GLM_POISSON_LOG && !(yn >= 0))
+      return fail("GLM target: poisson_log needs y >= 0 at row " + std::to_string(n));
+    if (g->offset && !std::isfinite(g->offset[n]))
+      return fail("GLM target: offset is not finite at row " + std::to_string(n));
+  }
+  const long long Np = (N + 255) / 256 * 256, Dp = (D + 31) / 32 * 32;
+  std::vector<double> buf((size_t)(Dp + 2 * Np + Dp * Np), 0.0);
+  double* iv = buf.data();
+  double* y = iv + Dp;
+  double* off = y + Np;
+  double* xt = off + Np;
+  for (long long j = 0; j < D; ++j) iv[j] = 1.0 / (g->prior_sd[j] * g->prior_sd[j]);
+  for (long long n = 0; n < N; ++n) {
+    y[n] = g->y[n];
+    off[n] = g->offset ? g->offset[n] : 0.0;
+    for (long long j = 0; j < D; ++j) xt[j * Np + n] = g->x[n * D + j];
+  }
+  const int rc = upload_as(dt, buf.data(), buf.size(), d_buf);
+  if (rc) return rc;
+  out->glm = *d_buf;
+  out->glm_family = g->family;
+  out->glm_dp = (int)Dp;
+  out->glm_n = N;
+  out->glm_np = Np;
+  return GM_OK;
+}
+
 int gm::build_target(const gm_target* t, gm_dtype dt, long long dim, TargetDev* out, void** d_mu,
                      void** d_prec) {
   GM_REQ(t != nullptr, "target is NULL");
@@ -448,6 +507,11 @@ int gm::build_target(const gm_target* t, gm_dtype dt, long long dim, TargetDev* 
       int rc = upload_as(dt, pv.data(), pv.size(), d_prec);
       if (rc) return rc;
       out->params = *d_prec;
+      break;
+    }
+    case GM_TARGET_GLM: {
+      const int rc = build_glm(t, dt, dim, out, d_prec);
+      if (rc) return rc;
       break;
     }
     default:
@@ -632,6 +696,8 @@ static int create_common(int kind, const gm_target* target, gm_dtype dtype, int6
   GM_REQ(chain_offset >= 0 && chain_offset + n_chains <= 0xffffffffLL,
          "global chain ids must fit in 32 bits");
   GM_REQ(dim <= 1024 || kind == K_HMC, "dim > 1024 is supported by the HMC sampler only");
+  GM_REQ(!(target && target->kind == GM_TARGET_GLM && kind == K_MH),
+         "GLM target: not supported by the MH sampler (HMC and NUTS take it)");
   gm_sampler* s = new gm_sampler();
   s->kind = kind;
   s->dt = dtype;
@@ -658,6 +724,8 @@ static int create_common(int kind, const gm_target* target, gm_dtype dtype, int6
       set_error(msg);
       return rc;
     }
+  } else if (target->kind == GM_TARGET_GLM) {
+    // (its own layouts: default_layout's choice stands for every sampler)
   } else if (kind == K_NUTS && dim > 16 && dim <= 64) {
     // NUTS: two coordinates per lane halve the lanes that wait in each
     // per-chain reduction and put twice the chains in a wave (measured at
@@ -694,6 +762,19 @@ int gm_hmc_create(const gm_target* target, gm_dtype dtype, int64_t n_chains, int
   if (rc) return rc;
   (*out)->eps = step_size;
   (*out)->L = (int)n_leapfrog;
+  if (target->kind == GM_TARGET_GLM) {
+    // the GLM target is compiled into hmc_adapt_kernel only: the sampler has
+    // the per-chain state from the start (every step size step_size, the
+    // identity metric), and the frozen mode returns the plain kernel's bits
+    rc = hmc_adapt_ensure(*out);
+    if (rc) {
+      const std::string msg = gm_last_error();
+      gm_destroy(*out);
+      *out = nullptr;
+      set_error(msg);
+      return rc;
+    }
+  }
   return GM_OK;
 }
 
@@ -745,6 +826,14 @@ int gm_sampler_set_layout(gm_sampler* s, int32_t lanes, int32_t elems) {
   GM_REQ(s->tg.kind != GM_TARGET_CUSTOM || (lanes == 1 && elems == s->D),
          "CUSTOM targets run one chain per lane (layout 1 x dim)");
   if (s->tg.kind == GM_TARGET_CUSTOM) return GM_OK;
+  if (s->tg.kind == GM_TARGET_GLM) {
+    GM_REQ(lanes <= 64, "GLM target: wide layouts (lanes > 64) are not supported");
+    GM_REQ(glm_layout_supported(lanes, elems), "GLM target: layout (lanes, elems) is not one of 16x2, 64x1, 64x2");
+    GM_REQ((long long)lanes * elems >= s->D, "lanes*elems must cover dim");
+    s->lay.lanes = lanes;
+    s->lay.elems = elems;
+    return GM_OK;
+  }
   const bool wide = lanes > 64;
   if (wide && s->kind == K_NUTS) {  // one chain per workgroup (nuts_wide.hip)
     GM_REQ(nuts_wide_layout_supported(lanes, elems), "wide NUTS layout (lanes, elems) is not compiled in");
@@ -1320,6 +1409,8 @@ int gm_hmc_set_adaptation(gm_sampler* s, int32_t mode, double target_accept, int
   if (mode == 0) {  // back to the scalar step size, the identity metric and hmc_kernel
     hmc_dense_free(s);
     hmc_adapt_free(s);
+    // (a GLM sampler has no plain kernel: the per-chain state again, in its start state)
+    if (s->tg.kind == GM_TARGET_GLM) return hmc_adapt_ensure(s);
     return GM_OK;
   }
   const size_t C = (size_t)s->C;
@@ -1826,6 +1917,8 @@ int gm_nuts_set_mass_adaptation(gm_sampler* s, int32_t mode, int64_t start_buffe
   GM_REQ(s->kind == K_NUTS, "not a NUTS sampler");
   GM_REQ(mode >= 0 && mode <= 2, "mode must be 0 (none), 1 (diagonal) or 2 (dense)");
   GM_REQ(start_buffer >= 0 && end_buffer >= 0 && initial_window >= 0, "window sizes must be >= 0");
+  GM_REQ(!(s->tg.kind == GM_TARGET_GLM && mode == 2 && s->D <= dense_max_dim),
+         "GLM target: the dense NUTS metric is not supported (identity or diagonal)");
   GM_HIP(hipSetDevice(s->device));
   GM_HIP(hipStreamSynchronize(s->stream));
   // dense only up to dense_max_dim, else diagonal (generic_nuts.rs:613-620)
@@ -1853,6 +1946,7 @@ int gm_nuts_set_metric_convention(gm_sampler* s, int32_t convention, int32_t poo
   GM_REQ(convention == 0 || convention == 1, "convention must be 0 (reference) or 1 (whitening)");
   GM_REQ(pooled == 0 || pooled == 1, "pooled must be 0 or 1");
   GM_REQ(!pooled || convention == 1, "a pooled metric needs the whitening convention");
+  GM_REQ(!(pooled && s->tg.kind == GM_TARGET_GLM), "GLM target: the pooled NUTS metric is not supported (per chain)");
   GM_REQ(!pooled || (s->D >= 2 && s->D <= GM_DENSE_MAX_DIM), "a pooled metric needs 2 <= dim <= 64");
   GM_HIP(hipSetDevice(s->device));
   GM_HIP(hipStreamSynchronize(s->stream));
@@ -2202,6 +2296,8 @@ int gm_state_load(gm_sampler* s, const void* in, uint64_t bytes) {
     case K_HMC:
       GM_REQ(h.eps == s->eps && h.L == s->L, "state blob is for a different step size / n_leapfrog");
       GM_REQ(h.mass_mode >= 0 && h.mass_mode <= 2, "corrupt state blob (per-chain state flag)");
+      GM_REQ(s->tg.kind != GM_TARGET_GLM || h.mass_mode == 1,
+             "GLM target: the state blob must carry the per-chain step sizes and diagonal metric");
       if (h.mass_mode == 2) {
         const Layout def = default_layout(s->D, s->dt, s->tg.kind);
         GM_REQ(s->D >= 2 && s->D <= GM_DENSE_MAX_DIM && s->lay.lanes == def.lanes && s->lay.elems == def.elems,

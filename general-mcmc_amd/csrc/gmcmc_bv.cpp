@@ -178,6 +178,7 @@ int gm_bv_target_create(const gm_target* target, gm_dtype dt, gm_bv_target** out
   *out = nullptr;
   BV_REQ(dtype_ok(dt), "bad dtype");
   BV_REQ(target != nullptr, "target is NULL");
+  BV_REQ(target->kind != GM_TARGET_GLM, "GLM target: not supported by gm_bv_target_create (use gm_target_logp_grad)");
   gm_bv_target* t = new gm_bv_target();
   t->dt = dt;
   const int rc = build_target(target, dt, target->dim, &t->tg, &t->d_mu, &t->d_prec);

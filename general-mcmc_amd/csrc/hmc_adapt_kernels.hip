@@ -29,6 +29,7 @@ hipError_t launch_hmc_adapt(gm_dtype dt, const TargetDev& tg, const Layout& lay,
       return jit_launch(jk, dt, tg, (unsigned)((a.h.C + 255) / 256), 256, 0, st, args);
     });
   }
+  if (tg.kind == GM_TARGET_GLM) return launch_glm_hmc_adapt(dt, tg, lay, a, mode, st, ev);  // glm_kernels.hip
   using Fn = hipError_t (*)(const TargetDev&, const Layout&, const HmcAdaptLaunch&, hipStream_t, LaunchEvents);
   static const Fn table[2][3] = {
       {launch_hmc_adapt_f32_m0, launch_hmc_adapt_f32_m1, launch_hmc_adapt_f32_m2},

@@ -29,6 +29,7 @@
 #include "gm_jit.h"
 #include "gm_layouts.h"
 #include "nuts_launch.h"
+#include "glm_launch.h"
 #include "gm_nuts.h"
 #include "gm_track.h"
 
@@ -1094,6 +1095,8 @@ int nuts_run(NutsState& ns, gm_dtype dt, const TargetDev& tg, const Layout& lay,
       UserTargetArg ut{tg.params, tg.D};
       void* args[] = {&a, &ut};
       e = jit_launch(rec ? JIT_NUTS_REC : JIT_NUTS, dt, tg, blocks, 256, lds, st, args);
+    } else if (tg.kind == GM_TARGET_GLM) {  // its own layouts and units (glm_nuts_part.inc)
+      e = launch_glm_nuts(dt, tg, lay, a, rec, st, budget);
     } else {
       e = nuts_launch_layout(dt, tg, lay, a, rec, st, budget);
     }

@@ -46,6 +46,7 @@ hipError_t launch_logp_grad(gm_dtype dt, const TargetDev& tg, const Layout& lay,
     void* args[] = {&nn, &D, &xx, &lp, &gr, &ut};
     return jit_launch(JIT_LOGP, dt, tg, (unsigned)((n + 255) / 256), 256, 0, st, args);
   }
+  if (tg.kind == GM_TARGET_GLM) return launch_glm_logp_grad(dt, tg, lay, n, x, logp, grad, st);  // glm_kernels.hip
   if (layout_is_wide(lay)) {
     if (n == 0) return hipSuccess;
     return dispatch_wide(dt, tg, lay, [&]<class T, int E, class TG>(TG t) -> hipError_t {

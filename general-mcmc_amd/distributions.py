@@ -13,6 +13,8 @@ log-density with an analytic gradient (no autodiff graph, hmc.rs:42-61).
     CustomTarget          a user target (the Target / GradientTarget traits,
                           distributions.rs:67-110) as HIP source, compiled at
                           run time into the sampler kernels
+    GLM                   Bayesian logistic / Poisson regression on a data set
+                          (no counterpart in the reference)
 """
 from __future__ import annotations
 
@@ -217,3 +219,88 @@ class CustomTarget(_TargetBase):
         lib = _lib.load()
         _lib.check(lib.gm_custom_target_check(self.source.encode(), _lib.dtype_code(dtype), self.dim,
                                               self._KINDS[sampler]))
+
+
+class GLM(_TargetBase):
+    """Generalised linear model with canonical link and an independent Gaussian
+    prior; the chain's position is the coefficient vector theta [D]:
+
+        eta_n = sum_j X[n][j] theta_j + offset_n
+        logp  = sum_n (y_n eta_n - A(eta_n)) - 0.5 sum_j theta_j^2 / prior_sd_j^2
+
+    family "bernoulli_logit" (0 <= y <= 1; A = log(1 + exp(eta))) or
+    "poisson_log" (y >= 0; A = exp(eta); `offset` is the log exposure).
+    The intercept is a column of ones in X. Runs with HMC (and its warm-up)
+    and NUTS (identity or diagonal adaptive metric); 1 <= D <= 128."""
+
+    FAMILIES = {"bernoulli_logit": _lib.GM_GLM_BERNOULLI_LOGIT, "poisson_log": _lib.GM_GLM_POISSON_LOG}
+
+    def __init__(self, X, y, family: str = "bernoulli_logit", prior_sd=1.0, offset=None):
+        if family not in self.FAMILIES:
+            raise ValueError(f"GLM target: family must be one of {sorted(self.FAMILIES)}, got {family!r}")
+        X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
+        if X.ndim != 2:
+            raise ValueError("GLM target: X must be [n_rows, dim]")
+        n, d = X.shape
+        if n < 1:
+            raise ValueError("GLM target: n_rows must be >= 1")
+        if not 1 <= d <= 128:
+            raise ValueError("GLM target: dim must be in [1, 128]")
+        y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+        if y.shape != (n,):
+            raise ValueError(f"GLM target: y must be [n_rows] = [{n}], got {list(y.shape)}")
+        sd = np.asarray(prior_sd, dtype=np.float64)
+        if sd.ndim == 0:
+            sd = np.full(d, float(sd))
+        sd = np.ascontiguousarray(sd.reshape(-1))
+        if sd.shape != (d,):
+            raise ValueError(f"GLM target: prior_sd must be a scalar or [dim] = [{d}], got {list(sd.shape)}")
+        if offset is not None:
+            offset = np.ascontiguousarray(np.asarray(offset, dtype=np.float64).reshape(-1))
+            if offset.shape != (n,):
+                raise ValueError(f"GLM target: offset must be [n_rows] = [{n}], got {list(offset.shape)}")
+
+        def first(bad):  # index of the first True of a mask
+            return int(np.argmax(bad))
+
+        # the C side's checks, in its order and wording
+        bad = ~np.isfinite(sd)
+        if bad.any():
+            raise ValueError(f"GLM target: prior_sd is not finite at column {first(bad)}")
+        bad = ~(sd > 0)
+        if bad.any():
+            raise ValueError(f"GLM target: prior_sd must be > 0 at column {first(bad)}")
+        # rows: the first offending row; within it x, then y, its range, the offset
+        xb = ~np.isfinite(X)
+        yb = ~np.isfinite(y)
+        if family == "bernoulli_logit":
+            rb, rmsg = ~((y >= 0) & (y <= 1)) & ~yb, "GLM target: bernoulli_logit needs 0 <= y <= 1 at row {}"
+        else:
+            rb, rmsg = ~(y >= 0) & ~yb, "GLM target: poisson_log needs y >= 0 at row {}"
+        ob = ~np.isfinite(offset) if offset is not None else np.zeros(n, dtype=bool)
+        found = []
+        for rank, (mask, fmt) in enumerate(((xb.any(axis=1), None), (yb, "GLM target: y is not finite at row {}"),
+                                            (rb, rmsg), (ob, "GLM target: offset is not finite at row {}"))):
+            if mask.any():
+                r = first(mask)
+                found.append((r, rank, fmt.format(r) if fmt else
+                              f"GLM target: x is not finite at row {r}, column {first(xb[r])}"))
+        if found:
+            raise ValueError(min(found)[2])
+        self.X, self.y, self.prior_sd, self.offset = X, y, sd, offset
+        self.family = family
+        self.n_rows = n
+        self.dim = d
+
+    def _fill(self, t, dim):
+        dp = C.POINTER(C.c_double)
+        desc = _lib.gm_glm_desc()
+        desc.family = self.FAMILIES[self.family]
+        desc.n_rows = self.n_rows
+        desc.x = self.X.ctypes.data_as(dp)
+        desc.y = self.y.ctypes.data_as(dp)
+        desc.offset = self.offset.ctypes.data_as(dp) if self.offset is not None else None
+        desc.prior_sd = self.prior_sd.ctypes.data_as(dp)
+        t.kind = _lib.GM_TARGET_GLM
+        t.glm = C.pointer(desc)
+        return [desc, self.X, self.y, self.offset, self.prior_sd]

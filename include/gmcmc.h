@@ -61,14 +61,46 @@ typedef enum gm_target_kind {
                                to D dims: logp = norm_const - 0.5 (x-mu)^T P (x-mu),
                                P = Sigma^-1 supplied row-major; also Gaussian2D as a
                                Target (distributions.rs:193-207) with norm_const = 0 */
-  GM_TARGET_CUSTOM = 4      /* user code (the reference's Target / GradientTarget
+  GM_TARGET_CUSTOM = 4,     /* user code (the reference's Target / GradientTarget
                                traits, distributions.rs:67-110): HIP source defining
                                  template <class T> __device__
                                  T gm_logp_grad(const T* x, T* g, const T* params);
                                for one chain (x, g of length GM_DIM, a macro = dim),
                                compiled at run time (hiprtc) into the sampler kernels;
                                one chain per lane, dim <= 256 */
+  GM_TARGET_GLM = 5         /* generalised linear model with canonical link and an
+                               independent Gaussian prior, described by gm_glm_desc
+                               (gm_target.glm); dim = number of columns, 1..128 */
 } gm_target_kind;
+
+/* GLM families (gm_glm_desc.family); eta_n = sum_j x[n][j] theta_j + offset_n */
+#define GM_GLM_BERNOULLI_LOGIT 1 /* A(eta) = max(eta,0) + log1p(exp(-|eta|)), mu = logistic(eta); 0 <= y <= 1 */
+#define GM_GLM_POISSON_LOG 2     /* A(eta) = mu(eta) = exp(eta); y >= 0; offset = log exposure */
+
+/* GM_TARGET_GLM:
+ *   logp  = sum_n ( y_n eta_n - A(eta_n) ) - 0.5 sum_j theta_j^2 / prior_sd_j^2
+ *   grad_j = sum_n x[n][j] ( y_n - mu(eta_n) ) - theta_j / prior_sd_j^2
+ * (additive constants that do not depend on theta are dropped; a non-finite
+ * log-density is not clamped: the proposal is rejected / the tree divergent).
+ * The arrays are host memory, copied to the device in the sampler's dtype when
+ * a sampler (or gm_target_logp_grad) is created, and may be freed afterwards.
+ * Creation returns GM_EINVAL, naming the first offending row or column, unless
+ * every x, y, offset and prior_sd is finite, y is in the family's range,
+ * prior_sd > 0, n_rows >= 1 and 1 <= dim <= 128.
+ * Takes gm_target_logp_grad, gm_hmc_create (per-chain step sizes, diagonal
+ * metric, their warm-up, statistics) and gm_nuts_create (identity or diagonal
+ * adaptive metric, either convention, per chain). MH, the dense HMC metric,
+ * the NUTS dense and pooled metrics, wide layouts and gm_bv_target_create
+ * return GM_EINVAL ("GLM target: ..."). */
+typedef struct gm_glm_desc {
+  int32_t family;         /* GM_GLM_BERNOULLI_LOGIT or GM_GLM_POISSON_LOG */
+  int32_t reserved;
+  int64_t n_rows;
+  const double* x;        /* [n_rows*dim] row-major design matrix */
+  const double* y;        /* [n_rows] */
+  const double* offset;   /* [n_rows] or NULL (all 0) */
+  const double* prior_sd; /* [dim] */
+} gm_glm_desc;
 
 typedef struct gm_target {
   int32_t kind;          /* gm_target_kind */
@@ -82,6 +114,12 @@ typedef struct gm_target {
   const char* source;    /* CUSTOM: HIP source of gm_logp_grad (copied) */
   const double* params;  /* CUSTOM: [n_params] copied to the device in the sampler dtype */
   int64_t n_params;      /* CUSTOM: passed to gm_logp_grad as `params` */
+  /* Appended after the struct's first release. The library reads this field
+   * only when kind == GM_TARGET_GLM, a kind that callers compiled against the
+   * shorter struct cannot set knowingly: their gm_target objects keep
+   * working unchanged. Callers that set GM_TARGET_GLM must be compiled
+   * against this header. */
+  const gm_glm_desc* glm; /* GLM: the model (copied at creation) */
 } gm_target;
 
 /* Compile a CUSTOM target's source for the sampler kernels without running it
