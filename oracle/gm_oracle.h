@@ -137,6 +137,17 @@ int or_nuts_step_f(const or_target* t, int lanes, int elems, int64_t C, int D, f
                    int max_depth, uint64_t seed, uint64_t step0, uint32_t chain_offset,
                    int64_t n_steps, int64_t m0, int64_t n_discard, int64_t* accepts,
                    int64_t* n_leapfrog, int threads);
+/* or_nuts_step with the tree depth of every chain's last transition (depth [C]). */
+int or_nuts_step_depth_d(const or_target* t, int lanes, int elems, int64_t C, int D, double* q,
+                         double* eps, double* eps_bar, double* h_bar, double* mu,
+                         double target_accept, int max_depth, uint64_t seed, uint64_t step0,
+                         uint32_t chain_offset, int64_t n_steps, int64_t m0, int64_t n_discard,
+                         int64_t* accepts, int64_t* n_leapfrog, int32_t* depth, int threads);
+int or_nuts_step_depth_f(const or_target* t, int lanes, int elems, int64_t C, int D, float* q,
+                         float* eps, float* eps_bar, float* h_bar, float* mu,
+                         double target_accept, int max_depth, uint64_t seed, uint64_t step0,
+                         uint32_t chain_offset, int64_t n_steps, int64_t m0, int64_t n_discard,
+                         int64_t* accepts, int64_t* n_leapfrog, int32_t* depth, int threads);
 /* ---- NUTS mass-matrix warmup (generic_nuts.rs:33-359, 897-921) ----
  * GenericNUTS::new_with_mass_matrix: Welford windows during warm-up, the
  * diagonal or dense metric, the probe + find_reasonable_epsilon re-start

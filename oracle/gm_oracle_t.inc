@@ -832,6 +832,7 @@ typedef struct {
   or_mass_state* ms;
   int64_t* sched_out;      /* [C][2] */
   int64_t m0;              /* progress == 2 (step): adaptation counter before the first step */
+  int32_t* depth;          /* NULL or [C]: the tree depth of each chain's last transition */
 } F(nuts_ctx);
 
 static void F(nuts_chains)(void* vctx, int64_t c0, int64_t c1) {
@@ -947,6 +948,7 @@ static void F(nuts_chains)(void* vctx, int64_t c0, int64_t c1) {
         sgo = top.s && (cv ? F(no_uturn)(&cx, qm, qp, vm, vp) : F(no_uturn_m)(&cx, qm, qp, pm, pp));
         ++j;
       }
+      if (a->depth) a->depth[c] = j;
       T eta = (T)1 / (T)(m + t0c);
       h_bar = ((T)1 - eta) * h_bar + eta * (delta - alpha / (T)n_alpha);
       if (m <= a->n_discard) {
@@ -1067,6 +1069,24 @@ int F(or_nuts_step)(const or_target* t, int lanes, int elems, int64_t C, int D, 
   F(nuts_ctx) a = {t, lanes, elems, C, D, q, eps, eps_bar, h_bar, mu, target_accept, max_depth,
                    seed, step0, chain_offset, n_steps, n_discard, 2, NULL,
                    accepts, n_leapfrog, NULL, NULL, NULL, m0};
+  parallel_chains(C, threads, F(nuts_chains), &a);
+  return 0;
+}
+
+/* or_nuts_step that also returns the tree depth of every chain's last
+ * transition (depth [C]); with n_steps = 1, the transition's. */
+int F(or_nuts_step_depth)(const or_target* t, int lanes, int elems, int64_t C, int D, T* q, T* eps,
+                          T* eps_bar, T* h_bar, T* mu, double target_accept, int max_depth,
+                          uint64_t seed, uint64_t step0, uint32_t chain_offset, int64_t n_steps,
+                          int64_t m0, int64_t n_discard, int64_t* accepts, int64_t* n_leapfrog,
+                          int32_t* depth, int threads) {
+  if (D < 1 || D > 1024 || lanes * elems < D || lanes * elems > 1024 || (lanes > 64 && lanes % 64) ||
+      max_depth < 1 || max_depth > 30)
+    return 1;
+  if (n_steps <= 0) return 0;
+  F(nuts_ctx) a = {t, lanes, elems, C, D, q, eps, eps_bar, h_bar, mu, target_accept, max_depth,
+                   seed, step0, chain_offset, n_steps, n_discard, 2, NULL,
+                   accepts, n_leapfrog, NULL, NULL, NULL, m0, depth};
   parallel_chains(C, threads, F(nuts_chains), &a);
   return 0;
 }

@@ -83,3 +83,53 @@ def synth(N, D, family, seed, offset=True, x_scale=None, theta_scale=1.0):
     else:
         y = rng.poisson(np.exp(np.clip(eta, -20, 5))).astype(np.float64)
     return X, y, off
+
+
+def bound(ref, dtype):
+    """8 (N + D) u: the factor of the scales in the evaluation bound (tests/test_gpu_glm.py)."""
+    return 8.0 * (ref.N + ref.D) * unit_roundoff(dtype)
+
+
+def perturbed(ref, tol, seed=1):
+    """ref.logp_grad with independent errors uniform in +-tol * scales on the log-density and on
+    every gradient entry: an evaluation that just meets the bound tol, for a transcription's
+    sensitivity to the rounding of the evaluation."""
+    prng = np.random.default_rng(seed)
+
+    def f(q):
+        lp, g = ref.logp_grad(q)
+        S, G = ref.scales(q)
+        with np.errstate(invalid="ignore"):  # (a rejected overflow: infinite scales)
+            return lp + tol * S * prng.uniform(-1, 1, lp.shape), g + tol * G * prng.uniform(-1, 1, g.shape)
+    return f
+
+
+# ---- the NUTS cases of tests/test_nuts_ref.py (CPU) and tests/test_gpu_glm.py (GPU) ----
+# (N, D, layout or None for the default): two and four column chunks at two row
+# passes, and three chunks with the second coordinate slot real
+NUTS_SHAPES = [(300, 33, None), (300, 128, None), (70, 65, (64, 2))]
+NUTS_RUN = dict(n_chains=4, n_collect=4, n_discard=6, seed=17, max_depth=6, target_accept=0.8)
+_nuts_cache = {}
+
+
+def nuts_case(N, D, family):
+    """(reference, gm.GLM arguments, x0 [4, D])."""
+    X, y, off = synth(N, D, family, 3)
+    x0 = 0.3 * np.random.default_rng(5).standard_normal((NUTS_RUN["n_chains"], D))
+    return GlmRef(X, y, family, 2.0, off), dict(X=X, y=y, family=family, prior_sd=2.0, offset=off), x0
+
+
+def nuts_reference(oracle, N, D, family):
+    """The float64 NUTS transcription (tests/_nuts_ref.py) of the case, a second run of it under
+    perturbed() at the float64 evaluation bound, and their deviation: (r, r2, sens), stacked
+    over chains. Computed once per case."""
+    from tests import _nuts_ref
+    key = (N, D, family)
+    if key not in _nuts_cache:
+        ref, _, x0 = nuts_case(N, D, family)
+        c = NUTS_RUN
+        args = (x0, -1.0, c["n_collect"], c["n_discard"], c["seed"], c["max_depth"], c["target_accept"])
+        r = _nuts_ref.stack(_nuts_ref.run(oracle, ref.logp_grad, *args))
+        r2 = _nuts_ref.stack(_nuts_ref.run(oracle, perturbed(ref, bound(ref, np.float64)), *args))
+        _nuts_cache[key] = (r, r2, _nuts_ref.deviation(r, r2))
+    return _nuts_cache[key]

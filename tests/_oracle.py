@@ -76,6 +76,9 @@ def load():
         getattr(lib, f"or_nuts_step_{sfx}").argtypes = [tp, _int, _int, _i64, _int, _vp, _vp, _vp,
                                                         _vp, _vp, _dbl, _int, _u64, _u64, _u32,
                                                         _i64, _i64, _i64, _vp, _vp, _int]
+        getattr(lib, f"or_nuts_step_depth_{sfx}").argtypes = [tp, _int, _int, _i64, _int, _vp, _vp, _vp,
+                                                              _vp, _vp, _dbl, _int, _u64, _u64, _u32,
+                                                              _i64, _i64, _i64, _vp, _vp, _vp, _int]
     for sfx in ("d", "f"):
         getattr(lib, f"or_nuts_mass_run_{sfx}").argtypes = [
             tp, _int, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _dbl, _int, _u64, _u64, _u32, _i64,
@@ -323,6 +326,22 @@ class Oracle:
             chain_offset, n_steps, m0, n_discard, _p(acc), _p(nlf), threads)
         assert rc == 0
         return q, acc, nlf
+
+    def nuts_step_depth(self, target: Target, q, state, target_accept, max_depth, seed, step0, n_steps,
+                        m0, n_discard, lanes, elems, chain_offset=0, threads=8):
+        """nuts_step, and the tree depth of every chain's last transition."""
+        q = np.array(q, copy=True, order="C")
+        C_, D = q.shape
+        acc = np.zeros(C_, dtype=np.int64)
+        nlf = np.zeros(C_, dtype=np.int64)
+        depth = np.zeros(C_, dtype=np.int32)
+        t = target.struct()
+        rc = getattr(self.lib, f"or_nuts_step_depth_{_sfx(q.dtype)}")(
+            C.byref(t), lanes, elems, C_, D, _p(q), _p(state["eps"]), _p(state["eps_bar"]),
+            _p(state["h_bar"]), _p(state["mu"]), target_accept, max_depth, seed, step0,
+            chain_offset, n_steps, m0, n_discard, _p(acc), _p(nlf), _p(depth), threads)
+        assert rc == 0
+        return q, acc, nlf, depth
 
     def split_rhat_ess(self, x, threads: int = 1):
         """split_rhat_mean_ess (stats.rs:439-450) of a [C, N, P] sample (cast

@@ -39,6 +39,7 @@ import math
 import numpy as np
 import pytest
 
+from tests import _nuts_ref
 from tests._oracle import Target
 from tests.test_oracle_nuts_forms import _mc_close, cfg3_target
 
@@ -49,7 +50,7 @@ for _f in ("exp", "log"):
 _libm.pow.restype = ctypes.c_double
 _libm.pow.argtypes = [ctypes.c_double, ctypes.c_double]
 
-TAG_MH_PROP, TAG_MH_ACC, TAG_NUTS_MOM, TAG_NUTS_INIT = 4, 5, 6, 11
+TAG_MH_PROP, TAG_MH_ACC = 4, 5
 
 
 # --------------------------------------------------------------------- MH
@@ -154,145 +155,10 @@ def test_mh_run_forms_statistics(oracle):
 # ------------------------------------------------------------------- NUTS
 def _ref_nuts_run(oracle, t, lanes, elems, x0, eps0, n_collect, n_discard, seed, max_depth=10,
                   target_accept=0.8):
-    """GenericNUTSChain::run / step / build_tree_with_mass / stop_criterion /
-    leapfrog_with_mass / find_reasonable_epsilon (generic_nuts.rs:700-1418)
-    under MassMatrix::identity, transcribed. Draws: the engine's RNG spec
-    (momenta TAG_NUTS_MOM, the transition's key block for Exp1 and the hashed
-    uniforms). The depth cap is the engine's documented deviation (the
-    reference has none). Returns per-chain samples, final position, step-size
-    state, accept and leapfrog counts."""
-    lib = oracle.lib
-    C_, D = x0.shape
-
-    def logp_and_grad(q):
-        lp, g = oracle.logp_grad(t, np.asarray(q), lanes, elems, np.float64)
-        return float(lp[0]), [float(v) for v in g[0]]
-
-    def kinetic(p):                          # :230-235
-        q = 0.0
-        for v in p:
-            q = q + v * v
-        return 0.5 * q
-
-    def dot(a, b):
-        s = 0.0
-        for x, y in zip(a, b):
-            s = s + x * y
-        return s
-
-    def stop_criterion(qm, qp, pm, pp):      # :1357-1378, identity
-        diff = [b - a for a, b in zip(qm, qp)]
-        return dot(diff, pm) >= 0.0 and dot(diff, pp) >= 0.0
-
-    counts = {"nlf": 0}
-
-    def leapfrog(q, p, g, eps):              # :1396-1418
-        half = 0.5
-        p = [pi + gi * (eps * half) for pi, gi in zip(p, g)]
-        q = [qi + vi * eps for qi, vi in zip(q, p)]
-        lp, g = logp_and_grad(q)
-        p = [pi + gi * (eps * half) for pi, gi in zip(p, g)]
-        counts["nlf"] += 1
-        return q, p, g, lp
-
-    def find_reasonable_epsilon(q0, p0):     # :1025-1102
-        eps, half = 1.0, 0.5
-        ulogp, g0 = logp_and_grad(q0)
-        q, p, g, ulogp1 = leapfrog(q0, p0, g0, eps)
-        k = 1.0
-        while not (math.isfinite(ulogp1) and all(math.isfinite(v) for v in g)):
-            k = k * half
-            q, p, g, ulogp1 = leapfrog(q0, p0, g0, eps * k)
-        eps = half * k * eps
-        la = ulogp1 - ulogp - (kinetic(p) - kinetic(p0))
-        a = 1.0 if la > _libm.log(half) else -1.0
-        while a * la > -a * _libm.log(2.0):
-            eps = eps * _libm.pow(2.0, a)
-            q, p, g, ulogp1 = leapfrog(q0, p0, g0, eps)
-            la = ulogp1 - ulogp - (kinetic(p) - kinetic(p0))
-        return eps
-
-    def build_tree(q, p, g, logu, v, j, eps, joint0, key, ctr):   # :1153-1341
-        if j == 0:
-            q1, p1, g1, lp1 = leapfrog(q, p, g, float(v) * eps)
-            joint = lp1 - kinetic(p1)
-            return dict(qm=q1, pm=p1, gm=g1, qp=q1, pp=p1, gp=g1, qprime=q1, gprime=g1, logp_prime=lp1,
-                        n=int(logu < joint), s=(logu - 1000.0) < joint,
-                        alpha=min(1.0, _libm.exp(joint - joint0)) if joint - joint0 == joint - joint0 else 1.0,
-                        n_alpha=1)
-        tr = build_tree(q, p, g, logu, v, j - 1, eps, joint0, key, ctr)
-        if tr["s"]:
-            if v == -1:
-                t2 = build_tree(tr["qm"], tr["pm"], tr["gm"], logu, v, j - 1, eps, joint0, key, ctr)
-                tr["qm"], tr["pm"], tr["gm"] = t2["qm"], t2["pm"], t2["gm"]
-            else:
-                t2 = build_tree(tr["qp"], tr["pp"], tr["gp"], logu, v, j - 1, eps, joint0, key, ctr)
-                tr["qp"], tr["pp"], tr["gp"] = t2["qp"], t2["pp"], t2["gp"]
-            u = lib.or_nuts_u_d(key, 64 + ctr[0])
-            ctr[0] += 1
-            if u < t2["n"] / max(tr["n"] + t2["n"], 1):
-                tr["qprime"], tr["gprime"], tr["logp_prime"] = t2["qprime"], t2["gprime"], t2["logp_prime"]
-            tr["n"] += t2["n"]
-            tr["s"] = tr["s"] and t2["s"] and stop_criterion(tr["qm"], tr["qp"], tr["pm"], tr["pp"])
-            tr["alpha"] = tr["alpha"] + t2["alpha"]
-            tr["n_alpha"] += t2["n_alpha"]
-        return tr
-
-    gamma, kappa, t0, delta = 0.05, 0.75, 10, target_accept
-    total = n_discard + n_collect - 1
-    out = []
-    for c in range(C_):
-        q = [float(v) for v in x0[c]]
-        eps, eps_bar, h_bar = float(eps0), 1.0, 0.0
-        # init_chain_state (:731-753)
-        p_init = [lib.or_normal_d(seed, c, 0, TAG_NUTS_INIT, i) for i in range(D)]
-        if abs(eps + 1.0) <= 2.220446049250313e-16:
-            eps = find_reasonable_epsilon(q, p_init)
-        mu = _libm.log(10.0 * eps)
-        counts["nlf"] = 0  # the leapfrog count is the transitions' (the step-size search's are not counted)
-        samples = [list(q)] if n_discard == 0 else []
-        acc = 0
-        for s in range(total):
-            m = s + 1
-            key, w = oracle.nuts_key(seed, c, s)
-            p0 = [lib.or_normal_d(seed, c, s, TAG_NUTS_MOM, i) for i in range(D)]
-            logp, g0 = logp_and_grad(q)
-            joint = logp - kinetic(p0)
-            k = ((w[2] >> 5) << 26) | (w[3] >> 6)
-            exp1 = -lib.or_log_d((k + 1) * 1.1102230246251565e-16)
-            logu = joint - exp1
-            qm, qp, pm, pp, gm, gp = q, q, p0, p0, g0, g0
-            j, n, go, alpha, n_alpha = 0, 1, True, 0.0, 0
-            ctr = [0]
-            while go and j < max_depth:
-                v = 1 if lib.or_nuts_u_d(key, 2 * j) < 0.5 else -1
-                if v == -1:
-                    tr = build_tree(qm, pm, gm, logu, v, j, eps, joint, key, ctr)
-                    qm, pm, gm = tr["qm"], tr["pm"], tr["gm"]
-                else:
-                    tr = build_tree(qp, pp, gp, logu, v, j, eps, joint, key, ctr)
-                    qp, pp, gp = tr["qp"], tr["pp"], tr["gp"]
-                alpha, n_alpha = tr["alpha"], tr["n_alpha"]
-                tmp = min(1.0, tr["n"] / n)
-                if tr["s"] and lib.or_nuts_u_d(key, 2 * j + 1) < tmp:
-                    q = tr["qprime"]
-                    acc += 1
-                n += tr["n"]
-                go = tr["s"] and stop_criterion(qm, qp, pm, pp)
-                j += 1
-            eta = 1.0 / (m + t0)
-            h_bar = (1.0 - eta) * h_bar + eta * (delta - alpha / n_alpha)
-            if m <= n_discard:
-                eps = _libm.exp(mu - math.sqrt(m) / gamma * h_bar)
-                eta = _libm.pow(float(m), -kappa)
-                eps_bar = _libm.exp((1.0 - eta) * _libm.log(eps_bar) + eta * _libm.log(eps))
-            else:
-                eps = eps_bar
-            if 0 <= (s + 1) - n_discard < n_collect:
-                samples.append(list(q))
-        out.append(dict(samples=np.array(samples), q=np.array(q), eps=eps, eps_bar=eps_bar, h_bar=h_bar, mu=mu,
-                        acc=acc, nlf=counts["nlf"]))
-    return out
+    """The transcription of identity-metric NUTS (tests/_nuts_ref.py) on a
+    built-in target: the log-density is the oracle's."""
+    return _nuts_ref.run(oracle, lambda q: oracle.logp_grad(t, q, lanes, elems, np.float64), x0, eps0, n_collect,
+                         n_discard, seed, max_depth, target_accept)
 
 
 @pytest.mark.parametrize("eps0", [-1.0, 0.3], ids=["find_eps", "given_eps"])

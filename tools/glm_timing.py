@@ -32,50 +32,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-# params: [N, family, iv[D], offset[N], y[N], X[N][D] row-major]
-CUSTOM_SOURCE = r"""
-__device__ inline float glm_l1p(float v) { return log1pf(v); }
-__device__ inline double glm_l1p(double v) { return log1p(v); }
-template <class T>
-__device__ T gm_logp_grad(const T* x, T* g, const T* p) {
-  const int N = (int)p[0];
-  const int fam = (int)p[1];
-  const T* iv = p + 2;
-  const T* off = iv + GM_DIM;
-  const T* y = off + N;
-  const T* X = y + N;
-  T lp = (T)0;
-#pragma unroll
-  for (int j = 0; j < GM_DIM; ++j) g[j] = (T)0;
-  for (int n = 0; n < N; ++n) {
-    const T* xr = X + (long long)n * GM_DIM;
-    T eta = off[n];
-#pragma unroll
-    for (int j = 0; j < GM_DIM; ++j) eta = gm::gfma(xr[j], x[j], eta);
-    T mu, A;
-    if (fam == 2) {
-      mu = gm::gexp(eta);
-      A = mu;
-    } else {
-      const T ae = eta < (T)0 ? -eta : eta;
-      const T em = gm::gexp(-ae);
-      mu = (eta >= (T)0 ? (T)1 : em) / ((T)1 + em);
-      A = (eta > (T)0 ? eta : (T)0) + glm_l1p(em);
-    }
-    lp = lp + (y[n] * eta - A);
-    const T r = y[n] - mu;
-#pragma unroll
-    for (int j = 0; j < GM_DIM; ++j) g[j] = gm::gfma(xr[j], r, g[j]);
-  }
-#pragma unroll
-  for (int j = 0; j < GM_DIM; ++j) {
-    const T pv = x[j] * iv[j];
-    lp = lp - ((T)0.5 * x[j]) * pv;
-    g[j] = g[j] - pv;
-  }
-  return lp;
-}
-"""
+from tests.custom_targets import GLM as CUSTOM_SOURCE  # noqa: E402
 
 PEAK = {"float32": 157.3e12, "float64": 78.65e12}
 
