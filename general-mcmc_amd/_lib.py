@@ -68,6 +68,11 @@ class gm_summary_out(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("mean", "sd", "quantiles", "rhat", "ess_bulk", "ess_tail")]
 
 
+class gm_glm_predict_out(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("eta_mean", "eta_sd", "mu_mean", "mu_sd", "lppd", "ll_mean", "ll_var",
+                                          "pointwise")]
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(gm_progress))
 
 _vp = C.c_void_p
@@ -157,6 +162,10 @@ SIGNATURES = {
                                 C.POINTER(gm_summary_out)]),
     "gm_rank_normalize": (_ip, [_vp, _ip, _i64, _i64, _i64, _i32, _vp, _vp]),
     "gm_summary_sort_plan": (_ip, [C.POINTER(_i32), _i32]),
+    "gm_glm_predict": (_ip, [C.POINTER(gm_glm_desc), _i64, _ip, _vp, _i64, C.POINTER(gm_glm_predict_out)]),
+    "gm_glm_predict_device": (_ip, [C.POINTER(gm_glm_desc), _i64, _ip, _vp, _i64, _i64,
+                                    C.POINTER(gm_glm_predict_out)]),
+    "gm_glm_predict_plan": (_ip, [C.POINTER(_i32), _i32]),
     "gm_comm_get_unique_id": (_ip, [_vp]),
     "gm_comm_init": (_ip, [_vp, _i32, _i32, C.POINTER(_vp)]),
     "gm_comm_destroy": (_ip, [_vp]),

@@ -304,3 +304,86 @@ class GLM(_TargetBase):
         t.kind = _lib.GM_TARGET_GLM
         t.glm = C.pointer(desc)
         return [desc, self.X, self.y, self.offset, self.prior_sd]
+
+    def predict(self, draws, X=None, y=None, offset=None, pointwise: bool = False):
+        """Posterior prediction over stored draws, computed on the GPU in the
+        draws' dtype and reduced over all of them in f64 (stats.GLMPrediction):
+        per data row the mean and sd of eta and of mu and, with y, the lppd and
+        the mean and variance of the pointwise log-likelihood (waic()).
+
+        draws: the DeviceSamples of a run on this model (used where they lie,
+        n_collect * n_chains draws in stored order) or a host array [..., dim]
+        (f32 and f64 are kept, anything else becomes f64).
+        X = None: the training rows with their y and offset. With a new X, y
+        and offset default to None; without y only eta and mu are returned.
+        pointwise: also the matrix ll [n_draws, n_rows] in the draws' dtype
+        (at most 2^31 bytes: pass the rows in blocks beyond that)."""
+        from ._sampler import DeviceSamples
+        from .stats import GLMPrediction
+        if X is None:
+            if y is not None or offset is not None:
+                raise ValueError("GLM predict: y and offset go with a new X")
+            X, y, offset = self.X, self.y, self.offset
+        else:
+            X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
+            if X.ndim != 2 or X.shape[1] != self.dim:
+                raise ValueError(f"GLM predict: X must be [n_rows, dim] with dim = {self.dim}")
+            n = X.shape[0]
+            if y is not None:
+                y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+                if y.shape != (n,):
+                    raise ValueError(f"GLM predict: y must be [n_rows] = [{n}], got {list(y.shape)}")
+            if offset is not None:
+                offset = np.ascontiguousarray(np.asarray(offset, dtype=np.float64).reshape(-1))
+                if offset.shape != (n,):
+                    raise ValueError(f"GLM predict: offset must be [n_rows] = [{n}], got {list(offset.shape)}")
+        m = X.shape[0]
+        if pointwise and y is None:
+            raise ValueError("GLM predict: the pointwise log-likelihood needs y")
+        dp = C.POINTER(C.c_double)
+        desc = _lib.gm_glm_desc()
+        desc.family = self.FAMILIES[self.family]
+        desc.n_rows = m
+        desc.x = X.ctypes.data_as(dp)
+        desc.y = y.ctypes.data_as(dp) if y is not None else None
+        desc.offset = offset.ctypes.data_as(dp) if offset is not None else None
+        desc.prior_sd = None
+
+        if isinstance(draws, DeviceSamples):
+            draws._check_live()
+            if draws.dim != self.dim:
+                raise ValueError(f"GLM predict: the samples have dim {draws.dim}, the model {self.dim}")
+            dtype = np.dtype(draws.dtype)
+            s = draws.n_collect * draws.n_chains
+            host = None
+        else:
+            host = np.asarray(draws)
+            if host.dtype not in (np.float32, np.float64):
+                host = host.astype(np.float64)
+            if host.ndim < 1 or host.shape[-1] != self.dim:
+                raise ValueError(f"GLM predict: draws must be [..., dim] with dim = {self.dim}")
+            dtype = host.dtype
+            s = int(np.prod(host.shape[:-1], dtype=np.int64))
+        if s < 1:
+            raise ValueError("GLM predict: no draws")
+        # before anything of that size is allocated
+        if pointwise and s * m * dtype.itemsize > 2 ** 31:
+            raise ValueError(f"GLM predict: the pointwise matrix ({s} x {m} x {dtype.itemsize} bytes) is larger than "
+                             "2^31 bytes: pass the rows in blocks")
+        if host is not None:
+            host = np.ascontiguousarray(host.reshape(s, self.dim))
+        names = ["eta_mean", "eta_sd", "mu_mean", "mu_sd"] + (["lppd", "ll_mean", "ll_var"] if y is not None else [])
+        f = {k: np.empty(m) for k in names}
+        pw = np.empty((s, m), dtype=dtype) if pointwise else None
+        out = _lib.gm_glm_predict_out(**{k: a.ctypes.data for k, a in f.items()})
+        out.pointwise = pw.ctypes.data if pw is not None else None
+        lib = _lib.require_gpu()
+        if host is None:
+            draws.owner.synchronize()  # an asynchronous run may still be writing them
+            _lib.check(lib.gm_glm_predict_device(C.byref(desc), self.dim, _lib.dtype_code(dtype), C.c_void_p(draws.ptr),
+                                                 s, self.dim, C.byref(out)))
+        else:
+            _lib.check(lib.gm_glm_predict(C.byref(desc), self.dim, _lib.dtype_code(dtype), _lib.ptr(host), s,
+                                          C.byref(out)))
+        return GLMPrediction(f["eta_mean"], f["eta_sd"], f["mu_mean"], f["mu_sd"], f.get("lppd"), f.get("ll_mean"),
+                             f.get("ll_var"), pw, s)

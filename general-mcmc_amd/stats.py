@@ -144,6 +144,85 @@ def sort_plan() -> dict:
 
 
 @dataclass
+class WAIC:
+    """GLMPrediction.waic(): elpd_i = lppd_i - ll_var_i per data row."""
+    elpd_waic: float
+    p_waic: float
+    se: float
+    waic: float
+    pointwise: np.ndarray
+    n_high_variance: int
+
+    def __str__(self) -> str:
+        rows = [f"{'elpd_waic':>10} {'se':>10} {'p_waic':>10} {'waic':>10}",
+                f"{self.elpd_waic:10.4g} {self.se:10.4g} {self.p_waic:10.4g} {self.waic:10.4g}"]
+        if self.n_high_variance:
+            rows.append(f"{self.n_high_variance} of {len(self.pointwise)} rows have a pointwise variance above "
+                        f"{GLMPrediction.HIGH_VARIANCE}")
+        return "\n".join(rows)
+
+
+@dataclass
+class GLMPrediction:
+    """GLM.predict: per data row, over all draws, in f64: mean and sd of the
+    linear predictor eta and of the mean response mu and, when y is known, the
+    log pointwise predictive density lppd and the mean and variance of the
+    pointwise log-likelihood (None without y). pointwise: the matrix
+    ll [n_draws, n_rows] in the draws' dtype, when asked for."""
+    eta_mean: np.ndarray
+    eta_sd: np.ndarray
+    mu_mean: np.ndarray
+    mu_sd: np.ndarray
+    lppd: np.ndarray | None
+    ll_mean: np.ndarray | None
+    ll_var: np.ndarray | None
+    pointwise: np.ndarray | None
+    n_draws: int
+
+    HIGH_VARIANCE = 0.4  # Vehtari, Gelman & Gabry 2017: WAIC is unreliable for rows above it
+
+    @property
+    def lppd_total(self) -> float:
+        self._need_y()
+        return float(np.sum(self.lppd))
+
+    def _need_y(self):
+        if self.lppd is None:
+            raise ValueError("GLM predict: lppd and WAIC need y")
+
+    def waic(self) -> WAIC:
+        self._need_y()
+        elpd = self.lppd - self.ll_var
+        m = len(elpd)
+        se = float(np.sqrt(m * np.var(elpd, ddof=1))) if m > 1 else float("nan")
+        total = float(np.sum(elpd))
+        return WAIC(total, float(np.sum(self.ll_var)), se, -2.0 * total, elpd,
+                    int(np.sum(self.ll_var > self.HIGH_VARIANCE)))
+
+    def __str__(self) -> str:
+        ll = self.lppd is not None
+        head = f"{'row':>6} {'eta_mean':>10} {'eta_sd':>10} {'mu_mean':>10} {'mu_sd':>10}"
+        if ll:
+            head += f" {'lppd':>10} {'ll_mean':>10} {'ll_var':>10}"
+        rows = [head]
+        for m in range(len(self.eta_mean)):
+            r = f"{m:>6} {self.eta_mean[m]:10.4g} {self.eta_sd[m]:10.4g} {self.mu_mean[m]:10.4g} {self.mu_sd[m]:10.4g}"
+            if ll:
+                r += f" {self.lppd[m]:10.4g} {self.ll_mean[m]:10.4g} {self.ll_var[m]:10.4g}"
+            rows.append(r)
+        if ll:
+            rows.append(f"lppd {self.lppd_total:.6g} over {self.n_draws} draws")
+        return "\n".join(rows)
+
+
+def predict_plan() -> dict:
+    """The GLM prediction's internal sizes (gm_glm_predict_plan)."""
+    v = (C.c_int32 * 3)()
+    _lib.check(_lib.load().gm_glm_predict_plan(v, 3))
+    return {"slab_draws": v[0], "tile_rows": v[1], "mfma_draws": v[2]}
+
+
+@dataclass
 class BasicStats:
     name: str
     min: float

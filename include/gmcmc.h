@@ -701,6 +701,53 @@ int gm_rank_normalize(const void* sample, gm_dtype dtype, int64_t n_chains, int6
  * min(cap, 4) values. */
 int gm_summary_sort_plan(int32_t* out, int32_t cap);
 
+/* ---- GLM posterior prediction over stored draws -------------------------
+ * Not in the reference. For a GLM (gm_glm_desc: family, x [n_rows][dim], an
+ * optional offset, an optional y; prior_sd is ignored and may be NULL) and
+ * n_draws coefficient vectors theta_s of dtype T, per draw s and row m in T:
+ *   eta = offset_m + sum_j x[m][j] theta_sj    (from offset_m, columns
+ *                                               ascending, one fma each)
+ *   mu  = logistic(eta) | exp(eta)             (no overflow for Bernoulli)
+ *   ll  = (y_m eta - A(eta)) + c_m             c_m = -lgamma(y_m + 1) for
+ *                                              poisson_log, 0 for
+ *                                              bernoulli_logit, computed in
+ *                                              float64 and rounded to T
+ * and per row m, reduced over all draws in float64:
+ *   eta_mean, eta_sd, mu_mean, mu_sd   sample mean and sd (ddof = 1)
+ *   lppd                               log((1/S) sum_s exp ll), running maximum
+ *   ll_mean, ll_var                    sample mean and variance (ddof = 1)
+ * With n_draws = 1 the sd and variance outputs are NaN. A row whose ll is
+ * -inf in every draw has lppd = -inf; -inf in some draws adds 0 to the lppd
+ * sum and makes ll_mean -inf and ll_var NaN; a NaN in a draw makes that
+ * row's outputs NaN. WAIC: elpd_m = lppd_m - ll_var_m.
+ * pointwise: the matrix ll [n_draws][n_rows] of dtype, copied to the host;
+ * refused when it would be larger than 2^31 bytes (pass the rows in blocks).
+ * lppd, ll_mean, ll_var and pointwise need y. eta is formed on the matrix
+ * cores; the split of the work depends on (n_draws, n_rows, dim, dtype) only,
+ * so repeated calls, the host and the device entry point, and two devices
+ * give the same bits.
+ * Every entry point returns GM_EINVAL before any device call, with
+ * gm_target's wording and first-offender rule for the model ("GLM target:
+ * ..."), for: a NULL model, x, draws or out; a bad family, dim outside
+ * [1, 128], n_rows outside [1, 2^24]; a bad dtype; n_draws < 1; stride_draw <
+ * dim; an output that needs y without y; a pointwise matrix over the cap; a
+ * non-finite x, y or offset; y outside the family's range.
+ * Host variant: draws is host [n_draws][dim]. Device variant: a device
+ * pointer to n_draws rows, stride_draw elements apart. */
+typedef struct gm_glm_predict_out { /* host arrays [n_rows], any may be NULL */
+  double *eta_mean, *eta_sd, *mu_mean, *mu_sd, *lppd, *ll_mean, *ll_var;
+  void* pointwise; /* host [n_draws][n_rows] of dtype, or NULL */
+} gm_glm_predict_out;
+int gm_glm_predict(const gm_glm_desc* model, int64_t dim, gm_dtype dtype,
+                   const void* draws /* host [n_draws][dim] */, int64_t n_draws,
+                   gm_glm_predict_out* out);
+int gm_glm_predict_device(const gm_glm_desc* model, int64_t dim, gm_dtype dtype,
+                          const void* dev_draws, int64_t n_draws, int64_t stride_draw,
+                          gm_glm_predict_out* out);
+/* The decomposition's sizes, for tests: [0] draws per slab, [1] data rows per
+ * workgroup tile, [2] draws per matrix-core tile. Writes min(cap, 3) values. */
+int gm_glm_predict_plan(int32_t* out, int32_t cap);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------
  * Chains are sharded in contiguous blocks; sampling needs no communication.
  * The only exchange is an RCCL all-gather of per-split-chain summaries for

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <random>
 #include <vector>
 
@@ -164,11 +165,50 @@ static void hmc_adapt_checks() {
   gm_test_sampler_free(s);
 }
 
+// gm_glm_predict*: every refusal comes before the first device call; the data
+// scans read exactly sized arrays to their last element (the offender is last).
+static void glm_predict_checks() {
+  const int64_t rows = 37, dim = 5;
+  std::vector<double> x((size_t)(rows * dim), 0.25), y((size_t)rows, 1.0), off((size_t)rows, 0.5), o((size_t)rows);
+  std::vector<float> th((size_t)(3 * dim), 0.1f);
+  gm_glm_desc g{};
+  g.family = GM_GLM_BERNOULLI_LOGIT;
+  g.n_rows = rows;
+  g.x = x.data();
+  g.y = y.data();
+  g.offset = off.data();
+  gm_glm_predict_out out{};
+  out.eta_mean = o.data();
+  out.lppd = o.data();
+  off.back() = std::numeric_limits<double>::infinity();
+  EXPECT(gm_glm_predict(&g, dim, GM_F32, th.data(), 3, &out) == GM_EINVAL, "predict: offset of the last row");
+  off.back() = 0.5;
+  y.back() = 2.0;
+  EXPECT(gm_glm_predict(&g, dim, GM_F32, th.data(), 3, &out) == GM_EINVAL, "predict: y of the last row");
+  y.back() = 1.0;
+  x.back() = std::numeric_limits<double>::quiet_NaN();
+  EXPECT(gm_glm_predict_device(&g, dim, GM_F64, th.data(), 3, dim, &out) == GM_EINVAL, "predict: last x");
+  g.y = nullptr;
+  g.offset = nullptr;
+  EXPECT(gm_glm_predict(&g, dim, GM_F32, th.data(), 3, &out) == GM_EINVAL, "predict: lppd without y");
+  out.lppd = nullptr;
+  EXPECT(gm_glm_predict(&g, dim, GM_F32, th.data(), 3, &out) == GM_EINVAL, "predict: last x, no y, no offset");
+  x.back() = 0.25;
+  EXPECT(gm_glm_predict(&g, dim, GM_F32, th.data(), 0, &out) == GM_EINVAL, "predict: no draws");
+  EXPECT(gm_glm_predict_device(&g, dim, GM_F32, th.data(), 3, dim - 1, &out) == GM_EINVAL, "predict: stride");
+  EXPECT(gm_glm_predict(&g, dim, GM_F32, th.data(), 3, nullptr) == GM_EINVAL, "predict: null out");
+  EXPECT(gm_glm_predict(nullptr, dim, GM_F32, th.data(), 3, &out) == GM_EINVAL, "predict: null model");
+  int32_t plan[3] = {0, 0, 0};
+  EXPECT(gm_glm_predict_plan(plan, 3) == GM_OK && plan[0] > 0 && plan[2] == 16, "predict plan");
+  EXPECT(gm_glm_predict_plan(plan, -1) == GM_EINVAL, "predict plan cap");
+}
+
 int main() {
   state_blobs();
   gauss_from_cov();
   argument_checks();
   hmc_adapt_checks();
+  glm_predict_checks();
   std::printf("%s\n", fails ? "ASAN HOST CHECKS FAILED" : "asan host checks ok");
   return fails ? 1 : 0;
 }
