@@ -13,7 +13,7 @@ from .distributions import (GLM, CustomTarget, DenseGaussian, DiffableGaussian2D
 from .hmc import HMC, HMCAdaptConfig
 from .metropolis_hastings import MetropolisHastings, MHAdaptConfig
 from .nuts import NUTS, MassMatrix, NUTSChain, NUTSMassMatrixConfig
-from .stats import (BasicStats, ChainStats, GLMPrediction, MultiChainTracker, Progress, RunStats, SamplerStats,
+from .stats import (BasicStats, ChainStats, GLMLoo, GLMPrediction, MultiChainTracker, Progress, RunStats, SamplerStats,
                     StatsSummary, Summary, basic_stats, rank_normalize, split_rhat_mean_ess, summary)
 
 __all__ = [
@@ -23,5 +23,5 @@ __all__ = [
     "init_with_seed", "split_rhat_mean_ess", "basic_stats", "BasicStats", "RunStats", "GMError",
     "batch_vector", "MultiChainTracker", "ChainStats", "Progress", "NUTSMassMatrixConfig", "MassMatrix",
     "HMCAdaptConfig", "MHAdaptConfig", "Summary", "summary", "rank_normalize", "SamplerStats", "StatsSummary",
-    "GLMPrediction",
+    "GLMPrediction", "GLMLoo",
 ]

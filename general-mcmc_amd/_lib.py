@@ -73,6 +73,11 @@ class gm_glm_predict_out(C.Structure):
                                           "pointwise")]
 
 
+class gm_glm_loo_out(C.Structure):
+    _fields_ = [("elpd_loo", C.c_void_p), ("pareto_k", C.c_void_p), ("tail", C.c_void_p),
+                ("tail_len", C.c_int64), ("n_nonfinite", C.c_int64)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(gm_progress))
 
 _vp = C.c_void_p
@@ -166,6 +171,10 @@ SIGNATURES = {
     "gm_glm_predict_device": (_ip, [C.POINTER(gm_glm_desc), _i64, _ip, _vp, _i64, _i64,
                                     C.POINTER(gm_glm_predict_out)]),
     "gm_glm_predict_plan": (_ip, [C.POINTER(_i32), _i32]),
+    "gm_glm_loo": (_ip, [C.POINTER(gm_glm_desc), _i64, _ip, _vp, _i64, _dbl, _i64, C.POINTER(gm_glm_loo_out)]),
+    "gm_glm_loo_device": (_ip, [C.POINTER(gm_glm_desc), _i64, _ip, _vp, _i64, _i64, _dbl, _i64,
+                                C.POINTER(gm_glm_loo_out)]),
+    "gm_glm_loo_plan": (_ip, [_ip, _i64, _i64, _dbl, _i64, C.POINTER(_i64), _i32]),
     "gm_comm_get_unique_id": (_ip, [_vp]),
     "gm_comm_init": (_ip, [_vp, _i32, _i32, C.POINTER(_vp)]),
     "gm_comm_destroy": (_ip, [_vp]),

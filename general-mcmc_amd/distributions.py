@@ -387,3 +387,62 @@ class GLM(_TargetBase):
                                           C.byref(out)))
         return GLMPrediction(f["eta_mean"], f["eta_sd"], f["mu_mean"], f["mu_sd"], f.get("lppd"), f.get("ll_mean"),
                              f.get("ll_var"), pw, s)
+
+    def loo(self, draws, reff: float = 1.0, tail: bool = False, workspace_bytes: int = 0):
+        """PSIS-LOO over stored draws, computed on the GPU (stats.GLMLoo): per
+        training row the Pareto-smoothed leave-one-out elpd and the Pareto
+        shape k of its importance ratios, from the pointwise log-likelihood of
+        predict() (same bits); the lppd beside them is predict()'s.
+
+        draws: as for predict(), at most 2^24 of them.
+        reff: the relative efficiency of the draws, a positive scalar; the tail
+        has min(floor(0.2 S), ceil(3 sqrt(S / reff))) values.
+        tail: also the sorted raw tail [n_rows, tail_len], f64, ascending.
+        workspace_bytes: the bound of the device workspace (0: the default,
+        stats.loo_plan()); the result does not depend on it."""
+        from ._sampler import DeviceSamples
+        from .stats import GLMLoo, loo_plan
+        reff = float(reff)
+        if not (np.isfinite(reff) and reff > 0):
+            raise ValueError("GLM loo: reff must be finite and > 0")
+        n = self.n_rows
+        if isinstance(draws, DeviceSamples):
+            draws._check_live()
+            if draws.dim != self.dim:
+                raise ValueError(f"GLM loo: the samples have dim {draws.dim}, the model {self.dim}")
+            dtype, host = np.dtype(draws.dtype), None
+            s = draws.n_collect * draws.n_chains
+        else:
+            host = np.asarray(draws)
+            if host.dtype not in (np.float32, np.float64):
+                host = host.astype(np.float64)
+            if host.ndim < 1 or host.shape[-1] != self.dim:
+                raise ValueError(f"GLM loo: draws must be [..., dim] with dim = {self.dim}")
+            dtype = host.dtype
+            s = int(np.prod(host.shape[:-1], dtype=np.int64))
+            host = np.ascontiguousarray(host.reshape(s, self.dim))
+        if s < 1:
+            raise ValueError("GLM loo: no draws")
+        # every refusal comes before any device work: the plan refuses what the call would
+        m = loo_plan(dtype, s, n, reff, workspace_bytes)["tail_len"]
+        pred = self.predict(draws if host is None else host)  # lppd
+        elpd, k = np.empty(n), np.empty(n)
+        tl = np.empty((n, m)) if tail else None
+        out = _lib.gm_glm_loo_out(elpd_loo=elpd.ctypes.data, pareto_k=k.ctypes.data,
+                                  tail=tl.ctypes.data if tail else None)
+        dp = C.POINTER(C.c_double)
+        desc = _lib.gm_glm_desc()
+        desc.family = self.FAMILIES[self.family]
+        desc.n_rows = n
+        desc.x = self.X.ctypes.data_as(dp)
+        desc.y = self.y.ctypes.data_as(dp)
+        desc.offset = self.offset.ctypes.data_as(dp) if self.offset is not None else None
+        desc.prior_sd = None
+        lib = _lib.require_gpu()
+        if host is None:
+            _lib.check(lib.gm_glm_loo_device(C.byref(desc), self.dim, _lib.dtype_code(dtype), C.c_void_p(draws.ptr), s,
+                                             self.dim, reff, int(workspace_bytes), C.byref(out)))
+        else:
+            _lib.check(lib.gm_glm_loo(C.byref(desc), self.dim, _lib.dtype_code(dtype), _lib.ptr(host), s, reff,
+                                      int(workspace_bytes), C.byref(out)))
+        return GLMLoo(elpd, k, pred.lppd, tl, int(out.tail_len), int(out.n_nonfinite), s)

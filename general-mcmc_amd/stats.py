@@ -223,6 +223,72 @@ def predict_plan() -> dict:
 
 
 @dataclass
+class GLMLoo:
+    """GLM.loo: PSIS-LOO per data row, f64. elpd_loo and pareto_k are NaN for a
+    row with a non-finite pointwise log-likelihood (n_nonfinite of them);
+    pareto_k is +inf where nothing could be fitted. lppd is GLM.predict's;
+    tail [n_rows, tail_len] is the sorted raw tail, when asked for."""
+    elpd_loo: np.ndarray
+    pareto_k: np.ndarray
+    lppd: np.ndarray
+    tail: np.ndarray | None
+    tail_len: int
+    n_nonfinite: int
+    n_draws: int
+
+    @property
+    def elpd_loo_sum(self) -> float:
+        return float(np.sum(self.elpd_loo))
+
+    @property
+    def p_loo(self) -> float:
+        return float(np.sum(self.lppd - self.elpd_loo))
+
+    @property
+    def se(self) -> float:
+        m = len(self.elpd_loo)
+        return float(np.sqrt(m * np.var(self.elpd_loo, ddof=1))) if m > 1 else float("nan")
+
+    @property
+    def looic(self) -> float:
+        return -2.0 * self.elpd_loo_sum
+
+    @property
+    def k_threshold(self) -> float:
+        """min(1 - 1 / log10(S), 0.7), Vehtari et al. 2024"""
+        with np.errstate(divide="ignore"):
+            return float(min(1.0 - 1.0 / np.log10(float(self.n_draws)), 0.7))
+
+    @property
+    def bad_rows(self) -> np.ndarray:
+        """Rows with pareto_k above k_threshold (+inf counts, NaN does not)."""
+        with np.errstate(invalid="ignore"):
+            return np.flatnonzero(self.pareto_k > self.k_threshold)
+
+    @property
+    def n_bad_k(self) -> int:
+        return int(len(self.bad_rows))
+
+    def __str__(self) -> str:
+        rows = [f"{'elpd_loo':>10} {'se':>10} {'p_loo':>10} {'looic':>10}",
+                f"{self.elpd_loo_sum:10.4g} {self.se:10.4g} {self.p_loo:10.4g} {self.looic:10.4g}"]
+        if self.n_bad_k:
+            rows.append(f"{self.n_bad_k} of {len(self.elpd_loo)} rows have a Pareto k above {self.k_threshold:.3g}")
+        if self.n_nonfinite:
+            rows.append(f"{self.n_nonfinite} rows have a non-finite pointwise log-likelihood")
+        return "\n".join(rows)
+
+
+def loo_plan(dtype=np.float32, n_draws: int = 1, n_rows: int = 1, reff: float = 1.0, workspace_bytes: int = 0) -> dict:
+    """The split of a GLM.loo call (gm_glm_loo_plan), without a device."""
+    v = (C.c_int64 * 7)()
+    _lib.check(_lib.load().gm_glm_loo_plan(_lib.dtype_code(dtype), n_draws, n_rows, float(reff), int(workspace_bytes),
+                                           v, 7))
+    return {"tail_len": v[0], "group_rows": v[1], "workspace_bytes": v[2], "row_bytes": v[3],
+            "default_workspace_bytes": v[4], "max_draws": v[5], "sort_slots": v[6]}
+
+
+@dataclass
 class BasicStats:
     name: str
     min: float

@@ -748,6 +748,72 @@ int gm_glm_predict_device(const gm_glm_desc* model, int64_t dim, gm_dtype dtype,
  * workgroup tile, [2] draws per matrix-core tile. Writes min(cap, 3) values. */
 int gm_glm_predict_plan(int32_t* out, int32_t cap);
 
+/* ---- GLM PSIS-LOO over stored draws -------------------------------------
+ * Not in the reference. Pareto-smoothed importance-sampling leave-one-out
+ * (Vehtari, Simpson, Gelman, Yao & Gabry 2024) per data row m of a GLM with y,
+ * from the pointwise log-likelihood ll_s (s = 1 .. S = n_draws) of
+ * gm_glm_predict: same operations, same dtype T, same bits. In float64:
+ *   lw_s = -ll_s - max_s(-ll_s)
+ *   M    = min(floor(0.2 S), ceil(3 sqrt(S / reff)))        (tail_len)
+ *   M < 5: pareto_k = +inf, nothing is smoothed. Otherwise the tail is the M
+ *   largest lw, cutoff = max(largest lw outside the tail, log(DBL_MIN)),
+ *   x_j = exp(tail_j) - exp(cutoff), j = 1 .. M ascending. x_M <= 0 or
+ *   x_(floor(M/4 + 0.5)) <= 0: pareto_k = +inf, nothing is smoothed. Otherwise
+ *   the generalised Pareto fit of Zhang & Stephens (2009): m = 30 +
+ *   floor(sqrt M) grid points theta_j = 1/x_M + (1 - sqrt(m / (j - 0.5))) /
+ *   (3 x_(floor(M/4 + 0.5))), kappa(theta) = mean_i log1p(-theta x_i),
+ *   l_j = M (log(-theta_j / kappa_j) - kappa_j - 1), w_j = 1 / sum_j' exp(l_j'
+ *   - l_j), theta^ = sum_j theta_j w_j, k = kappa(theta^), sigma = -k / theta^,
+ *   then k <- (k M + 5) / (M + 10). A finite k replaces tail value j by
+ *   min(log(sigma expm1(-k log1p(-p_j)) / k + exp(cutoff)), 0), p_j =
+ *   (j - 0.5) / M (k = 0: -sigma log1p(-p_j)); a non-finite k leaves the tail
+ *   and is reported as it came out.
+ *   elpd_loo = logsumexp_s(lw_s + ll_s) - logsumexp_s(lw_s), smoothed lw.
+ * n_draws = 1 gives elpd_loo = ll_1 and pareto_k = +inf. A row with a
+ * non-finite ll (NaN, +inf or -inf) in any draw has elpd_loo = pareto_k = NaN
+ * (its tail too) and is counted in n_nonfinite.
+ * tail: the raw (unsmoothed) tail of every row, float64 [n_rows][tail_len]
+ * ascending; the caller sizes it with gm_glm_loo_plan. The lppd that p_loo
+ * needs is gm_glm_predict's.
+ * Workspace: rows are taken in groups of R, a multiple of 64; a group holds
+ * ll [R][n_draws rounded up to 4] of T, 2 P float64 slots a row (P the power
+ * of two >= tail_len + 1) and 20 bytes a row. R is the largest multiple of 64
+ * that workspace_bytes holds (0: the default, 2^32 + 2^28), at most n_rows rounded
+ * up to 64 and 2^20. n_draws <= 2^24; tail_len has no limit of its own. The
+ * workspace must hold 64 rows: at the default that is every n_draws up to
+ * 2^24 in f32 and up to about 8.8e6 in f64 (reff = 1); beyond it the caller
+ * passes a larger workspace_bytes (gm_glm_loo_plan [5] is the largest n_draws
+ * that fits). The bound covers the per-group buffers above only, not the model
+ * (x padded to 4 k-steps, offset, y, c of T) nor, in gm_glm_loo, the uploaded
+ * copy of the draws. elpd_loo is formed with one logarithm of the quotient of
+ * the two sums, not as the difference of two log-sums of the size of log S. No
+ * floating-point atomics; every sum has a fixed order that depends on
+ * (n_draws, tail_len) only, so repeated calls, the host and the device entry
+ * point, and any workspace_bytes give the same bits.
+ * GM_EINVAL before any device call, with gm_glm_predict's wording for the
+ * model ("GLM target: ..."), for everything gm_glm_predict refuses, and for:
+ * a NULL y; reff not finite or <= 0; n_draws > 2^24; workspace_bytes < 0 or
+ * too small for 64 rows (the message gives the bytes needed). */
+typedef struct gm_glm_loo_out {
+  double *elpd_loo, *pareto_k; /* host [n_rows], either may be NULL */
+  double* tail;                /* host [n_rows][tail_len], or NULL */
+  int64_t tail_len;            /* written: M */
+  int64_t n_nonfinite;         /* written: rows with a non-finite ll */
+} gm_glm_loo_out;
+int gm_glm_loo(const gm_glm_desc* model, int64_t dim, gm_dtype dtype,
+               const void* draws /* host [n_draws][dim] */, int64_t n_draws, double reff,
+               int64_t workspace_bytes, gm_glm_loo_out* out);
+int gm_glm_loo_device(const gm_glm_desc* model, int64_t dim, gm_dtype dtype,
+                      const void* dev_draws, int64_t n_draws, int64_t stride_draw, double reff,
+                      int64_t workspace_bytes, gm_glm_loo_out* out);
+/* The split of such a call, without a device: [0] tail_len, [1] rows per
+ * group, [2] workspace bytes used, [3] bytes per row, [4] the default
+ * workspace_bytes, [5] the largest n_draws (<= 2^24) of which this dtype, reff
+ * and workspace_bytes hold 64 rows, [6] sort slots per row. Writes
+ * min(cap, 7) values; refuses what the call would refuse of these arguments. */
+int gm_glm_loo_plan(gm_dtype dtype, int64_t n_draws, int64_t n_rows, double reff,
+                    int64_t workspace_bytes, int64_t* out, int32_t cap);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------
  * Chains are sharded in contiguous blocks; sampling needs no communication.
  * The only exchange is an RCCL all-gather of per-split-chain summaries for
